@@ -7,7 +7,8 @@ full fp64 RTI (shift -> RK4 + forward sensitivities -> Gauss-Newton
 condensing with fp64 MFMA -> interior-point QP -> expansion) per step.
 Synthetic, seeded instances; closed loop: the next step's
 measured state is the predicted state at t0 + dt of the current solution
-(openkite_amd/fleet.py).
+(openkite_amd/fleet.py), in episodes of ``--episode`` steps from the launch
+states (the default 30 + 3 window lies inside the first one).
 
 One process per GPU (torch.distributed / RCCL); the batch shards with no
 data-path collective (weak scaling); after each step the per-instance
@@ -16,7 +17,12 @@ fleet would publish them.  ``--gpus N`` without a launcher starts the N
 ranks itself (torch.distributed.run as a child process, before this process
 touches a GPU) and fails if the node has fewer than N GPUs.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task).
+A plain run sets up, warms up, times ``--steps`` steps and prints ONE JSON
+line on rank 0 (``value``, ``ms_per_step`` and the per-kernel means of the
+timed steps).  ``--dump-outputs DIR`` also writes the last timed step's
+results as DIR/<name>.npy (same arguments, same inputs, so two builds compare
+output for output).  ``--full`` adds the measurements that need runs of their
+own: the CPU baseline and the single-kite latencies.
 """
 from __future__ import annotations
 
@@ -40,6 +46,7 @@ METRIC = "NMPC RTI steps/sec, batch=4096 N=20 horizon, 1/2/4/8 MI355X"
 
 
 TIMING_STRIDE = 3
+EPISODE = 40                   # closed-loop steps before the fleet starts again (--episode)
 
 
 def parse(argv=None):
@@ -50,6 +57,13 @@ def parse(argv=None):
     # exactly as on the GPU (profiles/r05j_oracle_long_loop.txt)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
+    # episodes: past step ~45 of the nominal loop kites leave their envelope and
+    # hand the controller non-finite states, after which a run measures cold
+    # restarts that exit at once -- another workload (loop length)
+    ap.add_argument("--episode", type=int, default=EPISODE, metavar="E",
+                    help="closed-loop steps per episode (warm-up steps count): before every E-th step the fleet "
+                         "starts again from its launch states with a cold step, so any --steps measures the same "
+                         "transient and ends on finite plans; 0 = one unbroken loop")
     ap.add_argument("--batch", type=int, default=4096, help="instances per GPU")
     ap.add_argument("--horizon", type=int, default=20)
     ap.add_argument("--substeps", type=int, default=2)
@@ -80,10 +94,18 @@ def parse(argv=None):
                          "at N = 20 is the undamped every-node mode (DESIGN 2.1)")
     ap.add_argument("--soft-weight", type=float, default=None,
                     help="qp_kernel 3: exact-L1 weight of the state rows (default: the config's 1e3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the CPU baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take the measurements that need runs of their own: the CPU "
+                         "baseline (cpu_baseline) and the single-kite latencies (gpu_latency_batch1); a plain run "
+                         "leaves both null")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline and the single-kite latencies after all")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: budget of the CPU baseline sample")
     ap.add_argument("--latency-steps", type=int, default=1000,
-                    help="warm single-kite steps of the single-thread CPU latency (BASELINE config 1)")
+                    help="--full: warm single-kite steps of the single-thread CPU latency (BASELINE config 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (rank 0's shard: u0, traj, "
+                         "diag, status, and the next measured state x_next) as DIR/<name>.npy in float64")
     return ap.parse_args(argv)
 
 
@@ -330,6 +352,28 @@ def dominant_kernel_names(dom, qp_kernel):
     return {3: ("k_qp_ric",), 2: ("k_qp_tiled", "k_qp_lds"), 1: ("k_qp",)}[qp_kernel]
 
 
+DUMP_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, loop):
+    """--dump-outputs: what the last timed step handed back for this rank's
+    kites -- u0 (B, 4), traj (B, N + 1, 15), diag (B, 6), status (B) and the
+    next measured state x_next (B, 15) -- one float64 DIR/<name>.npy each.
+    Above DUMP_BYTES in all, a fixed seeded sample of the kites is written
+    instead, its indices as kite_index.npy."""
+    arrays = {"u0": loop.u0, "traj": loop.traj, "diag": loop.diag, "status": loop.status, "x_next": loop.x0}
+    arrays = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in arrays.items()}
+    B = arrays["u0"].shape[0]
+    per_kite = sum(a.size // B for a in arrays.values()) * 8 + 8
+    os.makedirs(path, exist_ok=True)
+    if B * per_kite > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(20261019).choice(B, DUMP_BYTES // per_kite, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["kite_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -447,8 +491,13 @@ def main():
     loop = FleetLoop(GpuStepper(ctx), torch.from_numpy(x0_host).to(dev), N, cfg.dt, ekf=args.ekf,
                      covariances=ok.ekf_default_covariances() if args.ekf else None, publisher=pub, noise=noise)
 
-    for _ in range(args.warmup):
-        loop.step()
+    def run_steps(first, count):
+        for i in range(first, first + count):
+            if args.episode > 0 and i > 0 and i % args.episode == 0:
+                loop.restart()
+            loop.step()
+
+    run_steps(0, args.warmup)
     torch.cuda.synchronize(dev)
     if distributed:
         dist.barrier()
@@ -458,8 +507,7 @@ def main():
     # inside the timed region); the sampled steps give the per-kernel means
     ctx.timing_start((args.steps + TIMING_STRIDE - 1) // TIMING_STRIDE, TIMING_STRIDE)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loop.step()
+    run_steps(args.warmup, args.steps)
     torch.cuda.synchronize(dev)
     if distributed:
         dist.barrier()
@@ -470,6 +518,8 @@ def main():
     it_sum = ctx.qp_iteration_sum()
     b_steps, b_rows = ctx.state_bound_stats()
     status = loop.status.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loop)
 
     elapsed_max = max_over_ranks(elapsed, dev)
     total_rti = world * B * args.steps
@@ -517,12 +567,12 @@ def main():
                              "kernel alone on the step stream); frac_dense_count / frac_survey_count: the same "
                              "time priced with dense C and with SURVEY 8(d)'s F_qp; traffic = HBM bytes per "
                              f"launch from {tsrc}")
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(args, x0_host, args.cpu_seconds, wind)
-        # beside the CPU baseline only (the profiled runs pass --no-cpu-baseline and
-        # must see the batch launches alone)
-        lat1 = gpu_single_kite_latency(args, ok, x0_host[:40]) if world == 1 and not args.no_cpu_baseline else None
+        # --full only: the CPU baseline and, beside it, the single-kite latency
+        # take runs of their own (a plain run and the profiled runs see the
+        # batch launches alone)
+        extras = args.full and world == 1 and not args.no_cpu_baseline
+        cpu = cpu_baseline(args, x0_host, args.cpu_seconds, wind) if extras else None
+        lat1 = gpu_single_kite_latency(args, ok, x0_host[:40]) if extras else None
         workload = (f"batch={B}/GPU, N={N}, M={args.substeps}, full RTI fp64"
                     + (", fp32 sensitivities (BASELINE configs[3] precision)" if args.fp32_sens else "")
                     + (" + fused EKF (BASELINE configs[4])" if args.ekf else
@@ -556,7 +606,7 @@ def main():
                        "qp_soft_weight": cfg.qp_soft_weight,
                        # the measurement window: the synthetic loop is a transient
                        # (DESIGN 6), so numbers compare only at equal windows
-                       "timed_steps": args.steps, "warmup_steps": args.warmup,
+                       "timed_steps": args.steps, "warmup_steps": args.warmup, "episode_steps": args.episode,
                        "timing_stride": TIMING_STRIDE,
                        "backend": dist.get_backend() if distributed else "none"},
             "roofline": roofline,

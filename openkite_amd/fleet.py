@@ -11,7 +11,9 @@ One step of a fleet of kites on one rank:
          (kite_nmpc_step_device: KiteNMPF::computeControl, kiteNMPF.cpp:199-316).
   pub    optional publish of u0 + mpc_diagnostic of every kite to every rank
          (shard.Publisher: one all-gather, RCCL over xGMI / gloo on CPU).
-  plant  closed loop on synthetic data: the next measured state is the plan's
+  plant  closed loop on synthetic data (in episodes: ``restart`` puts every
+         kite back at its launch state, see bench.py --episode): the next
+         measured state is the plan's
          prediction at t0 + dt (trajectory node 1), and its position +
          attitude are the next EKF measurement.  With ``noise`` (a
          ``MeasurementNoise``) that state is disturbed before it is measured:
@@ -39,6 +41,9 @@ class GpuStepper:
     def rti(self, x0, u0, traj, diag, status):
         self.ctx.step_device(x0.data_ptr(), u0.data_ptr(), traj.data_ptr(), 0, diag.data_ptr(),
                              status.data_ptr())
+
+    def reset(self):
+        self.ctx.reset()
 
     def ekf(self, dt, xe, u3, P, z, W, V):
         self.ctx.ekf_step_device(xe.shape[0], dt, xe.data_ptr(), u3.data_ptr(), P.data_ptr(),
@@ -82,6 +87,7 @@ class FleetLoop:
         f64 = dict(dtype=torch.float64, device=dev)
         self.stepper, self.N, self.dt, self.pub, self.noise = stepper, N, dt, publisher, noise
         self.x0 = x0.clone()
+        self.x_init = x0.clone()
         self.u0 = torch.zeros((B, 4), **f64)
         self.traj = torch.zeros((B, N + 1, 15), **f64)
         self.diag = torch.zeros((B, 6), **f64)
@@ -95,10 +101,23 @@ class FleetLoop:
             self.W = torch.from_numpy(W.copy()).to(dev)
             self.V = torch.from_numpy(V.copy()).to(dev)
             self.P = torch.from_numpy(np.repeat(P0[None], B, axis=0)).to(dev)
+            self.P_init = self.P.clone()
             self.xe = self.x0[:, :13].clone()
             self.u3 = torch.zeros((B, 3), **f64)
             self.z = self.x0[:, 6:13].clone()
         self.gathered = None
+
+    def restart(self):
+        """Start the next episode: every kite back at its launch state, the
+        controller's next step a cold one (stepper.reset), the estimator at
+        its initial estimate and covariance.  All on the stream, no sync."""
+        self.stepper.reset()
+        self.x0.copy_(self.x_init)
+        self.u0.zero_()
+        if self.ekf:
+            self.xe.copy_(self.x_init[:, :13])
+            self.P.copy_(self.P_init)
+            self.z.copy_(self.x_init[:, 6:13])
 
     def step(self):
         if self.ekf:

@@ -42,6 +42,9 @@ class OracleStepper:
         u0.copy_(torch.from_numpy(u)); diag.copy_(torch.from_numpy(d)); status.copy_(torch.from_numpy(st))
         traj.copy_(torch.from_numpy(self.X))
 
+    def reset(self):
+        self.warm = 0
+
     def ekf(self, h, xe, u3, P, z, W, V):
         for b in range(xe.shape[0]):
             x, Pb = self.ffi.ekf_step(self.kp, xe[b].numpy(), u3[b].numpy(), h, P[b].numpy(),
@@ -156,3 +159,44 @@ def test_measurement_noise_disturbs_the_plant_reproducibly():
     assert torch.equal(runs[1], runs[2])                 # same seed, same draws
     assert not torch.equal(runs[1], runs[3])             # another seed
     assert not torch.equal(runs[0], runs[1])             # the noise reaches the loop
+
+
+def _episode(loop, steps):
+    out = []
+    for _ in range(steps):
+        loop.step()
+        out.append(torch.cat([loop.u0.cpu(), loop.diag.cpu(), loop.traj.cpu().flatten(1), loop.x0.cpu()], dim=1))
+    return torch.stack(out)
+
+
+@pytest.mark.parametrize("ekf", [False, True])
+def test_restart_repeats_the_first_episode(ekf):
+    """FleetLoop.restart (bench.py --episode): after it the loop runs its first
+    episode again -- a cold step from the launch states, the estimator at its
+    initial estimate and covariance -- bitwise, on the oracle stepper."""
+    loop = FleetLoop(OracleStepper(3), initial_states(0, 3), N, DT, ekf=ekf, covariances=covariances() if ekf else None)
+    first = _episode(loop, STEPS)
+    loop.restart()
+    assert torch.equal(_episode(loop, STEPS), first)
+    assert torch.isfinite(first).all()
+
+
+@pytest.mark.gpu
+def test_gpu_restart_repeats_the_first_episode():
+    """The same on the GPU stepper: two episodes of 3 steps (130 kites: more
+    than one block's worth, no multiple of 64) are bitwise the same sequence."""
+    import openkite_amd as ok
+    from openkite_amd.fleet import GpuStepper
+    from bench import synthetic_x0
+    B, Nh = 130, 20
+    cfg = ok.default_config(N=Nh)
+    g = ok.BatchNMPC(ok.load_properties(), cfg, B)
+    try:
+        g.set_stream(torch.cuda.current_stream().cuda_stream)
+        loop = FleetLoop(GpuStepper(g), torch.from_numpy(synthetic_x0(B, 0, g)).cuda(), Nh, cfg.dt)
+        first = _episode(loop, 3)
+        loop.restart()
+        assert torch.equal(_episode(loop, 3), first)
+        assert torch.isfinite(first).all()
+    finally:
+        g.close()

@@ -75,3 +75,38 @@ def test_rate_bound_option_sets_the_box_on_both_sides():
     assert d2["qp_form"] == 1 and d2["lm"] == 0.0 and d2["soft_weight"] == 1e6
     assert bench.apply_qp_options(ffi.node_config(N=20), bench.parse([]))["qp_form"] == 0
     assert bench.run_config_tag(a2)["qp_lm"] == 0.0
+
+
+def test_plain_run_is_lean_and_dump_outputs_writes_the_loop_state(tmp_path, monkeypatch):
+    """A plain run takes no measurement beyond its timed steps (--full off, no
+    dump); --dump-outputs writes the loop's result tensors as float64 .npy,
+    whole below the size cap and as a fixed seeded sample of the kites above it."""
+    import numpy as np
+    import torch
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.episode == bench.EPISODE == 40 and bench.parse(["--episode", "0"]).episode == 0
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full
+    B, N = 33, 5
+    g = torch.Generator().manual_seed(1)
+    loop = types.SimpleNamespace(u0=torch.rand((B, 4), generator=g, dtype=torch.float64),
+                                 traj=torch.rand((B, N + 1, 15), generator=g, dtype=torch.float64),
+                                 diag=torch.rand((B, 6), generator=g, dtype=torch.float64),
+                                 status=torch.arange(B, dtype=torch.int32),
+                                 x0=torch.rand((B, 15), generator=g, dtype=torch.float64))
+    bench.dump_outputs(str(tmp_path / "all"), loop)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in sorted(os.listdir(tmp_path / "all"))}
+    assert sorted(got) == ["diag", "status", "traj", "u0", "x_next"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["traj"], loop.traj.numpy()) and np.array_equal(got["x_next"], loop.x0.numpy())
+    assert np.array_equal(got["status"], np.arange(B, dtype=np.float64))
+    # above the cap: the same kites on every call, every array cut alike
+    per_kite = (4 + (N + 1) * 15 + 6 + 1 + 15 + 1) * 8
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * per_kite + 3)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), loop)
+    idx = np.load(tmp_path / "s1" / "kite_index.npy").astype(int)
+    assert idx.size == 10 and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "s2" / "kite_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "traj.npy"), loop.traj.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "s1" / "u0.npy"), loop.u0.numpy()[idx])
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) < 10 * per_kite + 6 * 128 + 3

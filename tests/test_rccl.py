@@ -23,12 +23,13 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def test_bench_rccl_branch_world1():
+def test_bench_rccl_branch_world1(tmp_path):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", f"--master-port={_free_port()}", os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "512", "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "512", "--no-cpu-baseline",
+           "--dump-outputs", str(tmp_path / "out")]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -36,3 +37,12 @@ def test_bench_rccl_branch_world1():
     assert out["config"]["backend"] == "nccl" and out["config"]["allgather"] is True
     assert out["n_gpus"] == 1 and out["value"] > 0
     assert out["status_nan"] == 0
+    # a run without --full takes none of the extra measurements, --steps is the
+    # timed window, and --dump-outputs holds the last timed step's results
+    assert out["cpu_baseline"] is None and out["gpu_latency_batch1"] is None
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    import numpy as np
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("u0", "traj", "diag", "status", "x_next")}
+    assert got["traj"].shape == (512, 21, 15) and got["u0"].shape == (512, 4) and got["status"].shape == (512,)
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in got.values())
+    assert np.array_equal(got["x_next"], got["traj"][:, 1, :]) and not (got["status"].astype(int) & 1).any()

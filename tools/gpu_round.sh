@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -x -q -s > $OUT/pytest_gpu.log 2>&1 || { echo "pytest failed"; exit 1; }
 fi
-timeout -k 10 300 python bench.py --steps 30 --warmup 3 --cpu-seconds 10 --qp-kernel $QK $EXTRA > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 3 --cpu-seconds 10 --qp-kernel $QK $EXTRA > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d $OUT/prof -o ktrace --output-format csv -- python bench.py --steps 30 --warmup 3 --no-cpu-baseline --qp-kernel $QK $EXTRA > $OUT/prof_bench.log 2>&1 || { echo "rocprof failed"; exit 1; }
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -T -d $OUT/pmc_fetch -o fetch --output-format csv -- python bench.py --steps 30 --warmup 3 --no-cpu-baseline --qp-kernel $QK $EXTRA > $OUT/pmc_fetch.log 2>&1 || { echo "pmc fetch failed"; exit 1; }
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -T -d $OUT/pmc_write -o write --output-format csv -- python bench.py --steps 30 --warmup 3 --no-cpu-baseline --qp-kernel $QK $EXTRA > $OUT/pmc_write.log 2>&1 || { echo "pmc write failed"; exit 1; }

@@ -15,5 +15,5 @@ timeout -k 10 200 $B --rate-bound 3 --qp-kernel 3 > $OUT/n20_ric_w3.json 2> $OUT
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -T -d $OUT/prof_ric_w3 -o ktrace --output-format csv -- $B --rate-bound 3 --qp-kernel 3 > $OUT/prof_ric_w3.log 2>&1 || { echo "prof ric w3 failed"; exit 1; }
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -T -d $OUT/prof_lazy_w3 -o ktrace --output-format csv -- $B --rate-bound 3 > $OUT/prof_lazy_w3.log 2>&1 || { echo "prof lazy w3 failed"; exit 1; }
 timeout -k 10 200 $B --horizon 40 --ekf > $OUT/config5.json 2> $OUT/config5.err || { echo "config5 failed"; exit 1; }
-timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; exit 1; }
+timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; exit 1; }
 echo done

@@ -20,5 +20,5 @@ timeout -k 10 300 python bench.py --batch 512 --horizon 40 --ekf --no-cpu-baseli
 python -c "import json;d=json.load(open('$OUT/bench_config5_512.json'));print('config5-512',d['value'],d['ms_per_step'],d['kernel_ms_per_step'],d['qp_main_kernel_ms_per_step'],d['qp_mean_iterations'])"
 timeout -k 10 300 python bench.py --horizon 40 --ekf --no-cpu-baseline > $OUT/bench_config5_4096.json 2> $OUT/bench_config5_4096.err || { echo bench5 4096 failed; exit 1; }
 python -c "import json;d=json.load(open('$OUT/bench_config5_4096.json'));print('config5-4096',d['value'],d['ms_per_step'],d['kernel_ms_per_step'],d['qp_main_kernel_ms_per_step'],d['qp_mean_iterations'])"
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; exit 1; }
 python -c "import json;d=json.load(open('$OUT/bench.json'));print('headline 20+5',d['value'],d['ms_per_step'],d['qp_main_kernel_ms_per_step'],d['qp_mean_iterations'],d['roofline']['frac'],d['gpu_latency_batch1']['median_ms'] if d.get('gpu_latency_batch1') else None)"
