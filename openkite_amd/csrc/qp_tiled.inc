@@ -522,6 +522,7 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
     // while max((1 - a) rmax, mu) >= QP_REC_THR (mu above the stall floor) an
     // iteration scales the previous residual vectors instead of forming H w,
     // C w and C' z -- below it, and so for every freeze decision, exactly.
+    // First solve only: the re-solves with lazy rows evaluate them every time.
     double a_prev = 0.0, rmax_prev = INFINITY;
     auto residuals = [&](bool may_rec) __attribute__((always_inline)) -> double {
         // mu first (the same terms in the same order as the exact pass summed them)
@@ -795,7 +796,12 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
     for (int round = LAZY ? 1 : 0; more; ++round) {
     iters = C.K;
     for (int it = 0; it < C.K; ++it) {
-        const double mu = residuals(it > 0);
+        // the lazy instance only re-solves with state-bound rows: exact residuals
+        // there.  Such a re-solve starts far outside its new rows and can run into
+        // the cap K; under the recursion the capped iterate then follows rounding
+        // (the oracle's own plan moved by up to 3e-3 under a 1e-15 relative change
+        // of its inputs, 1.7e-6 with exact residuals; tests/test_envelope.py)
+        const double mu = residuals(!LAZY && it > 0);
         QP_MARK(1);
         if (resid < IPM_FREEZE || resid != resid || mu < IPM_MU_FLOOR) { iters = it; break; }   // converged, poisoned or stalled
 #pragma unroll

@@ -74,7 +74,8 @@ def node_config(N: int = 20, dt: float = 0.05) -> Dict:
                                       # multiple-shooting QP (qp_form 1, qp_kernel 3)
         soft_weight=1e3, lm=10.0,     # kite_nmpc_default_config qp_soft_weight, qp_lm
         qp_rec=1e-6 if N == 20 else 0.0,   # condensed IPM: recursive residuals above 1e-6 as k_qp_tiled
-                                           # (qp_kernel 2 at N = 20); 0 = exact each iteration (k_qp,
+                                           # (qp_kernel 2 at N = 20; first solve only, the lazy-row
+                                           # re-solves are exact); 0 = exact each iteration (k_qp,
                                            # k_qp_lds: qp_kernel 1, other horizons)
     )
 

@@ -125,20 +125,80 @@ def mpl(vals):
     return [float(v) for v in vals]
 
 
-def main():
-    prm = load_yaml(os.path.join(REPO, "data", "umx_radian.yaml"))
-    x, u, f = kite_symbolic(prm)
-    xs = list(x) + list(u)
-    fn = sp.lambdify(xs, f, modules="mpmath")
-    Jsym = sp.Matrix(f).jacobian(sp.Matrix(xs))
-    jfn = sp.lambdify(xs, Jsym, modules="mpmath")
+def matmul(Am, Bm):
+    n, m, p = len(Am), len(Bm), len(Bm[0])
+    return [[mp.fsum(Am[i][k] * Bm[k][j] for k in range(m)) for j in range(p)] for i in range(n)]
 
-    def f_mp(xv, uv):
-        return [mp.mpf(t) for t in fn(*xv, *uv)]
 
-    def jac_mp(xv, uv):
-        Jm = jfn(*xv, *uv)
+class MpModel:
+    """kite_symbolic lambdified for mpmath: f, the exact Jacobian d f / d [x,u],
+    the augmented 15-state system and one RK4 interval with its exact
+    sensitivities, all at mpmath's current working precision."""
+
+    def __init__(self, prm):
+        x, u, f = kite_symbolic(prm)
+        xs = list(x) + list(u)
+        self.fn = sp.lambdify(xs, f, modules="mpmath")
+        Jsym = sp.Matrix(f).jacobian(sp.Matrix(xs))
+        self.jfn = sp.lambdify(xs, Jsym, modules="mpmath")
+
+    def f_mp(self, xv, uv):
+        return [mp.mpf(t) for t in self.fn(*xv, *uv)]
+
+    def jac_mp(self, xv, uv):
+        Jm = self.jfn(*xv, *uv)
         return [[mp.mpf(Jm[i, j]) for j in range(16)] for i in range(13)]
+
+    def aug_f(self, x15, u4):
+        fk = self.f_mp(x15[:13], u4[:3])
+        return fk + [x15[14], u4[3]]
+
+    def aug_J(self, x15, u4):
+        Jk = self.jac_mp(x15[:13], u4[:3])
+        A = [[mp.mpf(0)] * 15 for _ in range(15)]
+        Bm = [[mp.mpf(0)] * 4 for _ in range(15)]
+        for i in range(13):
+            for j in range(13):
+                A[i][j] = Jk[i][j]
+            for j in range(3):
+                Bm[i][j] = Jk[i][13 + j]
+        A[13][14] = mp.mpf(1)
+        Bm[14][3] = mp.mpf(1)
+        return A, Bm
+
+    def rk4_sens(self, x15, u4, h, M):
+        """RK4 and its exact derivative (chain rule through the 4 stages)."""
+        aug_f, aug_J = self.aug_f, self.aug_J
+        xv = list(x15)
+        S = [[mp.mpf(1 if i == j else 0) for j in range(19)] for i in range(15)]   # d x / d [x0 u]
+        Eu = [[mp.mpf(0)] * 19 for _ in range(4)]
+        for j in range(4):
+            Eu[j][15 + j] = mp.mpf(1)
+        for _ in range(M):
+            ks, dks = [], []
+            xs, Ss = xv, S
+            for st in range(4):
+                k = aug_f(xs, u4)
+                A, Bm = aug_J(xs, u4)
+                dk = [[a + b for a, b in zip(r1, r2)] for r1, r2 in zip(matmul(A, Ss), matmul(Bm, Eu))]
+                ks.append(k); dks.append(dk)
+                if st < 3:
+                    c = h / 2 if st < 2 else h
+                    xs = [xi + c * ki for xi, ki in zip(xv, k)]
+                    Ss = [[S[i][j] + c * dk[i][j] for j in range(19)] for i in range(15)]
+            xv = [xv[i] + (h / 6) * (ks[0][i] + 2 * ks[1][i] + 2 * ks[2][i] + ks[3][i]) for i in range(15)]
+            S = [[S[i][j] + (h / 6) * (dks[0][i][j] + 2 * dks[1][i][j] + 2 * dks[2][i][j] + dks[3][i][j])
+                  for j in range(19)] for i in range(15)]
+        return xv, S
+
+
+def load_model():
+    return MpModel(load_yaml(os.path.join(REPO, "data", "umx_radian.yaml")))
+
+
+def main():
+    model = load_model()
+    f_mp, jac_mp, aug_f, rk4_sens = model.f_mp, model.jac_mp, model.aug_f, model.rk4_sens
 
     # ---- known-answer states (SURVEY.md 4) ----------------------------------
     states = []
@@ -171,51 +231,6 @@ def main():
         rhs_cases.append(dict(source=src, x=xv, u=uv, f=mpl(fv), J=[mpl(row) for row in J]))
 
     # ---- RK4 intervals with exact sensitivities -------------------------------
-    def aug_f(x15, u4):
-        fk = f_mp(x15[:13], u4[:3])
-        return fk + [x15[14], u4[3]]
-
-    def aug_J(x15, u4):
-        Jk = jac_mp(x15[:13], u4[:3])
-        A = [[mp.mpf(0)] * 15 for _ in range(15)]
-        Bm = [[mp.mpf(0)] * 4 for _ in range(15)]
-        for i in range(13):
-            for j in range(13):
-                A[i][j] = Jk[i][j]
-            for j in range(3):
-                Bm[i][j] = Jk[i][13 + j]
-        A[13][14] = mp.mpf(1)
-        Bm[14][3] = mp.mpf(1)
-        return A, Bm
-
-    def matmul(Am, Bm):
-        n, m, p = len(Am), len(Bm), len(Bm[0])
-        return [[mp.fsum(Am[i][k] * Bm[k][j] for k in range(m)) for j in range(p)] for i in range(n)]
-
-    def rk4_sens(x15, u4, h, M):
-        """RK4 and its exact derivative (chain rule through the 4 stages)."""
-        xv = list(x15)
-        S = [[mp.mpf(1 if i == j else 0) for j in range(19)] for i in range(15)]   # d x / d [x0 u]
-        Eu = [[mp.mpf(0)] * 19 for _ in range(4)]
-        for j in range(4):
-            Eu[j][15 + j] = mp.mpf(1)
-        for _ in range(M):
-            ks, dks = [], []
-            xs, Ss = xv, S
-            for st in range(4):
-                k = aug_f(xs, u4)
-                A, Bm = aug_J(xs, u4)
-                dk = [[a + b for a, b in zip(r1, r2)] for r1, r2 in zip(matmul(A, Ss), matmul(Bm, Eu))]
-                ks.append(k); dks.append(dk)
-                if st < 3:
-                    c = h / 2 if st < 2 else h
-                    xs = [xi + c * ki for xi, ki in zip(xv, k)]
-                    Ss = [[S[i][j] + c * dk[i][j] for j in range(19)] for i in range(15)]
-            xv = [xv[i] + (h / 6) * (ks[0][i] + 2 * ks[1][i] + 2 * ks[2][i] + ks[3][i]) for i in range(15)]
-            S = [[S[i][j] + (h / 6) * (dks[0][i][j] + 2 * dks[1][i][j] + 2 * dks[2][i][j] + dks[3][i][j])
-                  for j in range(19)] for i in range(15)]
-        return xv, S
-
     rk4_cases = []
     h_int, M_int = mp.mpf("0.05"), 2
     for idx in [0, 1, 4] + list(range(5, 13)):
