@@ -1201,7 +1201,9 @@ int kite_nmpc_get_qp(kite_nmpc_ctx* ctx, int32_t instance, double* H, double* h,
         HIP_TRY(hipMemcpyAsync(H, ctx->Hs + b * n * n, n * n * sizeof(double), hipMemcpyDeviceToHost, s));
     if (H && ctx->tiled) {
         // reassemble the full matrix from the C-layout tiles (lane l: column l&15,
-        // rows (l>>4) + 4r), H_ab and H_bb
+        // rows (l>>4) + 4r), H_ab and H_bb.  Element (r, l) of a tile sits at
+        // r * 64 + l (k_condense<NR>, N = 40) or, with a lane's register pairs
+        // adjacent, at (r / 2) * 128 + 2 l + r % 2 (k_condense20, N = 20)
         const size_t na = 4 * N, nt = N / 4, ntile = nt * (nt + 1) / 2;
         std::vector<double> tl(ntile * 256), ab(na * 2), bb(4);
         HIP_TRY(hipMemcpyAsync(tl.data(), ctx->Htl + b * ntile * 256, tl.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1214,7 +1216,7 @@ int kite_nmpc_get_qp(kite_nmpc_ctx* ctx, int32_t instance, double* H, double* h,
                 for (int r = 0; r < 4; ++r)
                     for (int l = 0; l < 64; ++l) {
                         const size_t gi = 16 * I + (l >> 4) + 4 * r, gj = 16 * J + (l & 15);
-                        const double v = tl[(size_t)t * 256 + r * 64 + l];
+                        const double v = tl[(size_t)t * 256 + (N == 20 ? (r / 2) * 128 + 2 * l + r % 2 : r * 64 + l)];
                         H[gi * n + gj] = v;
                         H[gj * n + gi] = v;
                     }

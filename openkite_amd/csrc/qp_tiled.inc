@@ -26,7 +26,7 @@
 // Optional phase profile (-DKITE_QP_PROF, tools only): shader-clock cycles per
 // phase summed over all instances into g_qp_prof.
 #ifdef KITE_QP_PROF
-__device__ unsigned long long g_qp_prof[16];
+__device__ unsigned long long g_qp_prof[24];
 #define QP_MARK(ph)                                                                  \
     do {                                                                             \
         const unsigned long long t_ = __builtin_amdgcn_s_memtime();                  \
@@ -39,9 +39,28 @@ __device__ unsigned long long g_qp_prof[16];
         sub[ph] += t_ - sub_t;                                                       \
         sub_t = t_;                                                                  \
     } while (0)
+// load-wait sub-markers of k_qp_tiled (g_qp_prof[16..21]): QP_WSUB closes a
+// segment; QP_WDRAIN first waits for every outstanding global load, so the
+// segment it closes is the exposed load wait at that point (the product build
+// waits there or at the first use a few instructions later)
+#define QP_WSUB(ph)                                                                  \
+    do {                                                                             \
+        const unsigned long long t_ = __builtin_amdgcn_s_memtime();                  \
+        prof_wsub[ph] += t_ - prof_wt;                                               \
+        prof_wt = t_;                                                                \
+    } while (0)
+#define QP_WSTART() do { prof_wt = __builtin_amdgcn_s_memtime(); } while (0)
+#define QP_WDRAIN(ph)                                                                \
+    do {                                                                             \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                             \
+        QP_WSUB(ph);                                                                 \
+    } while (0)
 #else
 #define QP_MARK(ph) do { } while (0)
 #define QP_SUB(ph) do { } while (0)
+#define QP_WSUB(ph) do { } while (0)
+#define QP_WSTART() do { } while (0)
+#define QP_WDRAIN(ph) do { } while (0)
 #endif
 
 constexpr int TLD = 17;        // LDS row stride of a 16 x 16 tile: conflict-free rows and columns
@@ -378,7 +397,9 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
 #ifdef KITE_QP_PROF
     unsigned long long prof_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long prof_sub[3] = {0, 0, 0};
+    unsigned long long prof_wsub[6] = {0, 0, 0, 0, 0, 0};
     unsigned long long prof_last = __builtin_amdgcn_s_memtime();
+    unsigned long long prof_wt = prof_last;
 #endif
     double* Xb = X + (size_t)b * (N + 1) * NX;
     double* Ub = U + (size_t)b * N * NU;
@@ -386,27 +407,62 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
     // ---- load the QP (H_aa tiles stay in global / L2: re-read per iteration) --
     const double* Hg = Htl + (size_t)b * QP_NTILE * 256;
     double4v Mt[QP_NTILE];
-    // compile-time trip counts (N == QN, n == 4 QN + 2 on this path): every
-    // load is issued before the first LDS store waits for one (a runtime loop
-    // would serialise 20 memory latencies)
-    {
-        double cv[QN];
+    // Every global load of the kite is issued here, before the first wait, in
+    // the order of use (the waits then drain in that order: the small vectors
+    // first, the 30 loads of H last), so a kite starts with one exposed round
+    // trip instead of one per group.  Compile-time trip counts (N == QN,
+    // n == 4 QN + 2 on this path); lanes past an array's end load a clamped
+    // element and drop it, so no load sits behind a branch.
+    // H_aa tiles -> Mt (lane order [tile][reg pair][lane][2]: a lane's registers
+    // r, r + 1 are adjacent, so a tile is two 16-byte loads per lane); they
+    // serve the residual mat-vec and then become the normal matrix
+    auto load_h = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int k = 0; k < QN; ++k) cv[k] = Cr[((size_t)b * QN + k) * (4 * QN + 2) + l];   // QNC == 64 == lanes
-        double hv[3];
+        for (int t = 0; t < QP_NTILE; ++t)
 #pragma unroll
-        for (int q2 = 0; q2 < 3; ++q2) {
-            const int e = l + 64 * q2;
-            hv[q2] = e < 2 * QNA ? Habp[((size_t)b * QNA + e % QNA) * 2 + e / QNA] : 0.0;
-        }
+            for (int p = 0; p < 2; ++p) {
+                const double2v v = *reinterpret_cast<const double2v*>(Hg + t * 256 + p * 128 + 2 * l);
+                Mt[t][2 * p] = v[0];
+                Mt[t][2 * p + 1] = v[1];
+            }
+    };
+    double cv[QN], habv[3], ubv[2], hsv[2], suv[2], lbuv[2], ubuv[2];
 #pragma unroll
-        for (int k = 0; k < QN; ++k) sC[k * QNC + l] = cv[k];
+    for (int k = 0; k < QN; ++k) cv[k] = Cr[((size_t)b * QN + k) * (4 * QN + 2) + l];   // QNC == 64 == lanes
 #pragma unroll
-        for (int q2 = 0; q2 < 3; ++q2)
-            if (l + 64 * q2 < 2 * QNA) sHab[l + 64 * q2] = hv[q2];
+    for (int q2 = 0; q2 < 3; ++q2) {
+        const int e = l + 64 * q2 < 2 * QNA ? l + 64 * q2 : 0;
+        habv[q2] = Habp[((size_t)b * QNA + e % QNA) * 2 + e / QNA];
     }
     const double hbb00 = Hbbp[(size_t)b * 4 + 0], hbb01 = Hbbp[(size_t)b * 4 + 1], hbb11 = Hbbp[(size_t)b * 4 + 3];
-    fill_bounds(C, l, sbnd);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int i = l + 64 * s;
+        // the control that bounds variable i (none for theta0 / thetadot0)
+        const int ue = i < 3 * N ? (i / 3) * NU + i % 3 : (i < 4 * N ? (i - 3 * N) * NU + 3 : 0);
+        ubv[s] = Ub[ue];
+        // its scale and bounds: lane-indexed, so loads like the rest (left in the
+        // slot loop below they would each wait for everything issued here)
+        const int c = i < 3 * N ? i % 3 : 3;
+        suv[s] = C.Su[c]; lbuv[s] = C.lbu[c]; ubuv[s] = C.ubu[c];
+        hsv[s] = hs[(size_t)b * n + (i < n ? i : 0)];
+    }
+    const double clv = clp[(size_t)b * N + (l < N ? l : 0)], cuv = cup[(size_t)b * N + (l < N ? l : 0)];
+    const double hmaxv = hmaxp[b];
+    // state-bound table sbnd[i] = lbx[i], sbnd[16 + i] = ubx[i]: read by
+    // next_round only, so the fast instance has none
+    double lbv = 0.0, ubxv = 0.0;
+    if constexpr (LAZY) { lbv = C.lbx[l < NX ? l : 0]; ubxv = C.ubx[l < NX ? l : 0]; }
+    load_h();
+    QP_WSUB(0);                                        // init: every load issued
+#pragma unroll
+    for (int k = 0; k < QN; ++k) sC[k * QNC + l] = cv[k];
+#pragma unroll
+    for (int q2 = 0; q2 < 3; ++q2)
+        if (l + 64 * q2 < 2 * QNA) sHab[l + 64 * q2] = habv[q2];
+    if constexpr (LAZY) {
+        if (l < NX) { sbnd[l] = lbv; sbnd[16 + l] = ubxv; }
+    }
 
     QPState<2> q;
     const bool has_lo = C.lo_fin != 0, has_hi = C.hi_fin != 0;
@@ -422,20 +478,15 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
         const int i = l + 64 * s;
         double lo = 0.0, hi = 0.0, hv = 0.0;
         if (i < n) {
-            if (i < 3 * N) {
-                const int k = i / 3, c = i % 3;
-                lo = C.Su[c] * (C.lbu[c] - Ub[k * NU + c]);
-                hi = C.Su[c] * (C.ubu[c] - Ub[k * NU + c]);
-            } else if (i < 4 * N) {
-                const int k = i - 3 * N;
-                lo = C.Su[3] * (C.lbu[3] - Ub[k * NU + 3]);
-                hi = C.Su[3] * (C.ubu[3] - Ub[k * NU + 3]);
+            if (i < 4 * N) {
+                lo = suv[s] * (lbuv[s] - ubv[s]);
+                hi = suv[s] * (ubuv[s] - ubv[s]);
             } else if (i == 4 * N) {
                 lo = -C.flex * C.Sx13; hi = C.flex * C.Sx13;
             } else {
                 lo = -C.flex * C.Sx14; hi = C.flex * C.Sx14;
             }
-            hv = hs[(size_t)b * n + i];
+            hv = hsv[s];
         }
         if (i < n) { sLb[i] = lo; sUb[i] = hi; sHv[i] = hv; }     // constants of the solve: LDS
         const double mar = 0.1 * (hi - lo);
@@ -447,9 +498,9 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
         q.su[s] = fmax(hi - q.w[s], IPM_S0);
         q.zl[s] = IPM_Z0; q.zu[s] = IPM_Z0;
     }
-    q.clo = row_lane ? clp[(size_t)b * N + l] : 0.0;
-    q.chi = row_lane ? cup[(size_t)b * N + l] : 0.0;
-    const double dscale = 1.0 / (1.0 + hmaxp[b]);
+    q.clo = row_lane ? clv : 0.0;
+    q.chi = row_lane ? cuv : 0.0;
+    const double dscale = 1.0 / (1.0 + hmaxv);
     double inI = 1.0 / (double)nI;
     wave_sync();
 
@@ -507,15 +558,6 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
         out[1] = 0.0;
     };
 
-    // H_aa tiles -> Mt (lane order [tile][reg][lane]); they serve the residual
-    // mat-vec and then become the normal matrix
-    auto load_h = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int t = 0; t < QP_NTILE; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Mt[t][r] = Hg[t * 256 + r * 64 + l];
-    };
-    load_h();
     double resid = 0.0;
     // Recursive residuals (oracle qp_ipm, cfg C_qp_rec = QP_REC_THR): with one
     // step length a for w, s, z the linear residuals shrink exactly by (1 - a);
@@ -614,6 +656,8 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
         wave_sync();
     };
     init_rows();
+    QP_WSUB(1);                                        // init: small vectors consumed (first waits done)
+    QP_WDRAIN(2);                                      // init: H arrived
 
     double sgl[2], sgu[2], sglo = 0.0, sghi = 0.0;
     double isl[2], isu[2], islo = 1.0, ishi = 1.0;     // reciprocal slacks of the current iterate
@@ -803,6 +847,7 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
         // of its inputs, 1.7e-6 with exact residuals; tests/test_envelope.py)
         const double mu = residuals(!LAZY && it > 0);
         QP_MARK(1);
+        QP_WSTART();
         if (resid < IPM_FREEZE || resid != resid || mu < IPM_MU_FLOOR) { iters = it; break; }   // converged, poisoned or stalled
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
@@ -828,6 +873,8 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
             sb1 = readlane_d(d1, QNA - 64 + 1);
         }
         wave_sync();
+        QP_WSUB(3);                                    // normal matrix: up to the first MFMA's wait
+        QP_WDRAIN(4);                                  // normal matrix: the reloaded H arrived
         {                                              // Mt = H_aa (loaded by residuals())
             // vx row k depends on the kite controls of intervals 0..k only
             // (columns < 3k + 3; the condensing leaves exact zeros past them):
@@ -890,6 +937,7 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
                 }
         }
         wave_sync();
+        QP_WSUB(5);                                    // normal matrix: MFMAs, diagonal, equilibration
         QP_MARK(2);
 #ifdef KITE_QP_PROF
         chol_tiles(Mt, sT, sP, l, prof_sub);
@@ -1000,6 +1048,7 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
             atomicAdd(&g_qp_prof[9], (unsigned long long)iters);
             atomicAdd(&g_qp_prof[10], 1ull);
             for (int i = 0; i < 3; ++i) atomicAdd(&g_qp_prof[11 + i], prof_sub[i]);
+            for (int i = 0; i < 6; ++i) atomicAdd(&g_qp_prof[16 + i], prof_wsub[i]);
         }
 #endif
         return;
@@ -1017,6 +1066,7 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
         atomicAdd(&g_qp_prof[9], (unsigned long long)iters);
         atomicAdd(&g_qp_prof[10], 1ull);
         for (int i = 0; i < 3; ++i) atomicAdd(&g_qp_prof[11 + i], prof_sub[i]);
+        for (int i = 0; i < 6; ++i) atomicAdd(&g_qp_prof[16 + i], prof_wsub[i]);
     }
 #endif
 }
@@ -1062,10 +1112,10 @@ __global__ __launch_bounds__(64, 1) void k_qp_tiled_lazy(ModelConst P, RtiConst 
 }
 
 #ifdef KITE_QP_PROF
-// tools only: read and clear the phase profile (16 x uint64)
+// tools only: read and clear the phase profile (24 x uint64)
 extern "C" int kite_debug_qp_profile(unsigned long long* out) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_qp_prof), sizeof(g_qp_prof)) != hipSuccess) return -1;
-    const unsigned long long z[16] = {};
+    const unsigned long long z[24] = {};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_qp_prof), z, sizeof(z)) != hipSuccess) return -1;
     return 0;
 }

@@ -12,6 +12,7 @@
 namespace kite {
 
 typedef double double4v __attribute__((ext_vector_type(4)));
+typedef double double2v __attribute__((ext_vector_type(2)));
 
 // Compiler barriers written as inline asm always hold one real instruction
 // (asm volatile("s_nop 0" ...)): the hazard recognizer counts each inline-asm

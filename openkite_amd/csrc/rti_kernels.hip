@@ -1123,7 +1123,8 @@ __global__ __launch_bounds__(64, 2) void k_condense20(RtiConst C, int B, const d
 #pragma unroll 1
     for (int k = 0; k <= N; ++k) node(k);
 
-    // scaled QP out: H_aa tiles (+ R diagonal) in the tiled QP's lane order,
+    // scaled QP out: H_aa tiles (+ R diagonal) in the tiled QP's lane order
+    // ([tile][reg pair][lane][2], one 16-byte store per pair),
     // H_ab / H_bb / h from the three extra columns; hmax = max |H|
     double lmax = 0.0;
 #pragma unroll
@@ -1131,15 +1132,20 @@ __global__ __launch_bounds__(64, 2) void k_condense20(RtiConst C, int B, const d
 #pragma unroll
         for (int J = 0; J <= I; ++J) {
             const int t = I * (I + 1) / 2 + J;
+            double ho[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int gi = 16 * I + (l >> 4) + 4 * r, gj = 16 * J + (l & 15);
                 double hv = acc[t][r];
                 if (gi == gj) hv += sRd[gi];
                 hv *= sScl[gi] * sScl[gj];
-                Htl[((size_t)b * QP_NTILE + t) * 256 + r * 64 + l] = hv;
+                ho[r] = hv;
                 lmax = fmax(lmax, fabs(hv));
             }
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+                *reinterpret_cast<double2v*>(Htl + ((size_t)b * QP_NTILE + t) * 256 + p * 128 + 2 * l) =
+                    double2v{ho[2 * p], ho[2 * p + 1]};
         }
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
@@ -1397,11 +1403,13 @@ constexpr int QP_LAZY_GRID = 256;                  // blocks of the lazy instanc
 // The fast instance thus has no re-solve loop (the back edge alone costs the
 // tiled kernel ~350 B/lane of spills) and the lazy one costs ~2 us when the
 // list is empty.
-// bound table (LDS): sbnd[i] = lbx[i], sbnd[16 + i] = ubx[i]
+// bound table (LDS): sbnd[i] = lbx[i], sbnd[16 + i] = ubx[i].  Lane i loads
+// its own pair (two independent loads, one wait) -- a loop over constant
+// indices compiled to 15 masked branches, each waiting for its scalar loads.
 __device__ __forceinline__ void fill_bounds(const RtiConst& C, int l, double* sbnd) {
-#pragma unroll
-    for (int i = 0; i < NX; ++i)
-        if (l == i) { sbnd[i] = C.lbx[i]; sbnd[16 + i] = C.ubx[i]; }
+    const int i = l < NX ? l : 0;
+    const double lb = C.lbx[i], ub = C.ubx[i];
+    if (l < NX) { sbnd[l] = lb; sbnd[16 + l] = ub; }
 }
 // Violations of the trajectory Xb + dxs -> viol[(k-1)*12 + (i-1)] (signed
 // normalised magnitude: > 0 below lb, < 0 above ub), then the `want` largest
