@@ -44,7 +44,11 @@ extern "C" {
                                    6: kernel_times / timing_read report a sixth
                                       entry, the main QP kernel alone;
                                    7: kite_nmpc_timing_start_sampled (events on
-                                      every stride-th step; no config change) */
+                                      every stride-th step; no config change);
+                                      additive, no version change: the plant
+                                      simulator (kite_nmpc_plant_set_params,
+                                      _plant_set_wind, _plant_step, _plant_step_device,
+                                      KITE_PLANT_NAN)                             */
 #define KITE_PATH_MAX_HARMONICS 8 /* Fourier path: harmonics per axis              */
 
 /* ---- error codes ------------------------------------------------------ */
@@ -268,6 +272,43 @@ int kite_nmpc_predict(kite_nmpc_ctx* ctx, int32_t count, const double* x15,
 int kite_nmpc_rk4_sens(kite_nmpc_ctx* ctx, int32_t count, const double* x15,
                        const double* u4, double tf, int32_t M, double* xnext,
                        double* A, double* B);
+
+/* ---- plant simulator (src/kite_model/simulator.cpp) ----------------------
+ * The plant the controller is flown against: the kite ODE of every instance
+ * integrated on the device under the held control, with a plant model, a wind
+ * and a gust per kite that the controller is not told about (model-plant
+ * mismatch).  The context owns the device copies of the plant constants and
+ * the plant wind.  With neither set the plant is the controller's own model
+ * without wind, i.e. what kite_nmpc_predict integrates.                     */
+#define KITE_PLANT_NAN 1   /* plant status bit: state went non-finite, kite frozen */
+
+/* Per-kite plant model.  count == batch: params[b] is kite b's plant;
+ * count == 1: one plant model for all; params == NULL: the controller's own
+ * parameters (the default).  Anything else, a non-finite field, mass <= 0 or a
+ * singular inertia matrix: KITE_EINVAL, and the previous setting is kept.     */
+int kite_nmpc_plant_set_params(kite_nmpc_ctx* ctx, const kite_params* params, int32_t count);
+
+/* Per-kite plant wind, B x 8: [W0x W0y W0z  Ax Ay Az  f_hz  phase_rad], world
+ * frame, m/s: W(t) = W0 + A sin(2 pi f t + phase).  NULL: none.  Independent
+ * of kite_nmpc_set_wind (what the controller's model assumes).  Non-finite
+ * entries: KITE_EINVAL, and the previous setting is kept.                    */
+int kite_nmpc_plant_set_wind(kite_nmpc_ctx* ctx, const double* wind8);
+
+/* Advance every kite's 13 plant states in place from time t0 over steps * h
+ * under the held control u4 (B x 4; T, dE, dR; the 4th is ignored), RK4 with
+ * `substeps` per step (simulator.cpp:43-51; the driver uses h = 0.02, 4).
+ * Substep k of the call starts at t0 + k (h / substeps): a call that starts
+ * where another ended continues it.  status (nullable): B words of
+ * KITE_PLANT_* bits, written (not OR-ed) on every call.  A kite whose state
+ * turns non-finite keeps its last finite state and is flagged; one that is
+ * non-finite on entry is left untouched and flagged.  h <= 0 or non-finite,
+ * steps < 1, substeps < 1, steps * substeps > 2^24, non-finite t0:
+ * KITE_EINVAL.                                                              */
+int kite_nmpc_plant_step(kite_nmpc_ctx* ctx, double* x13, const double* u4, double t0,
+                         double h, int32_t steps, int32_t substeps, int32_t* status);
+/* Same on device pointers, asynchronous on the context stream.              */
+int kite_nmpc_plant_step_device(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4, double t0,
+                                double h, int32_t steps, int32_t substeps, int32_t* d_status);
 
 /* ---- introspection (tests, profiling) ---------------------------------- */
 /* ---- reference formulation: Chebyshev collocation (chebyshev.hpp) -------

@@ -69,6 +69,12 @@ struct kite_nmpc_ctx {
     double *Htl = nullptr, *Hab = nullptr, *Hbb = nullptr;
     double* wind = nullptr;        // per-kite world-frame wind B x 3 (kite_nmpc_set_wind)
     bool has_wind = false;         // a nonzero wind is set: the WIND kernels run
+    // plant simulator (plant_kernels.hip; kite_nmpc_plant_*)
+    int plant_count = 0;           // 0: the controller's own model (mc); 1: plant_mc1 for all; B: plant_mc
+    ModelConst plant_mc1;          // count == 1
+    double* plant_mc = nullptr;    // count == B: per-kite constants, field-major [kModelConstDoubles][B]
+    double* plant_wind = nullptr;  // B x 8 [W0 | A | f | phase] (kite_nmpc_plant_set_wind)
+    int plant_wind_mode = 0;       // 0 none (or all zero), 1 constant wind (every A == 0), 2 gust
     double* wstep = nullptr;       // tiled path, 2 B n: physical QP step per kite (k_qp_tiled -> k_expand20), then
                                    // the scaled one (-> k_qp_tiled_lazy: round 0 handed over); N = 40:
                                    // round-0 solution of the kites k_qp_lds hands to k_qp_lds_lazy
@@ -281,7 +287,8 @@ int ensure_scratch(kite_nmpc_ctx* ctx, size_t bytes) {
 void free_ctx(kite_nmpc_ctx* ctx) {
     double** bufs[] = {&ctx->X, &ctx->U, &ctx->x0, &ctx->AB, &ctx->DEF, &ctx->Hs, &ctx->hs,
                        &ctx->Cr, &ctx->cl, &ctx->cu, &ctx->hmax, &ctx->u0, &ctx->diag, &ctx->kkt,
-                       &ctx->scratch, &ctx->Htl, &ctx->Hab, &ctx->Hbb, &ctx->wstep, &ctx->wind};
+                       &ctx->scratch, &ctx->Htl, &ctx->Hab, &ctx->Hbb, &ctx->wstep, &ctx->wind,
+                       &ctx->plant_mc, &ctx->plant_wind};
     for (double** p : bufs) if (*p) { (void)hipFree(*p); *p = nullptr; }
     if (ctx->dconst) { (void)hipFree(ctx->dconst); ctx->dconst = nullptr; }
     if (ctx->status) { (void)hipFree(ctx->status); ctx->status = nullptr; }
@@ -873,6 +880,120 @@ int kite_nmpc_predict(kite_nmpc_ctx* ctx, int32_t count, const double* x15, cons
     return run_items(ctx, {{x15, c * 15}, {u4, c * 4}}, {{x15_out, c * 15}},
                      [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
                          return kite::launch_predict(ctx->mc, count, i[0], i[1], h, steps, o[0], s);
+                     });
+}
+
+// ---- plant simulator (simulator.cpp) ----------------------------------------
+extern "C++" {
+namespace {
+// a plant model the kernels can integrate: every field finite, a positive
+// mass, an invertible inertia matrix, and finite derived constants
+bool plant_params_ok(const kite_params& p, ModelConst* out) {
+    static_assert(sizeof(kite_params) == 52 * sizeof(double), "kite_params holds 52 doubles");
+    const double* f = reinterpret_cast<const double*>(&p);
+    for (int i = 0; i < 52; ++i) if (!std::isfinite(f[i])) return false;
+    if (!(p.mass > 0.0)) return false;
+    if (!(p.Ixx * p.Izz - p.Ixz * p.Ixz != 0.0) || !(p.Iyy != 0.0)) return false;
+    const ModelConst m = make_model_const(p);
+    const double* g = reinterpret_cast<const double*>(&m);
+    for (int i = 0; i < kite::kModelConstDoubles; ++i) if (!std::isfinite(g[i])) return false;
+    *out = m;
+    return true;
+}
+
+int plant_args_ok(double t0, double h, int32_t steps, int32_t substeps) {
+    if (!(h > 0.0) || !std::isfinite(h) || !std::isfinite(t0) || steps < 1 || substeps < 1) return KITE_EINVAL;
+    if ((int64_t)steps * substeps > (int64_t)1 << 24) return KITE_EINVAL;
+    return KITE_OK;
+}
+
+hipError_t plant_launch(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4, double t0, double h, int32_t steps,
+                        int32_t substeps, int32_t* d_status, hipStream_t s) {
+    const ModelConst& P = ctx->plant_count == 1 ? ctx->plant_mc1 : ctx->mc;
+    return kite::launch_plant(P, ctx->plant_count == ctx->B && ctx->plant_count > 1 ? ctx->plant_mc : nullptr, ctx->B,
+                              ctx->plant_wind_mode, ctx->plant_wind, d_x13, d_u4, t0, h / substeps, steps, substeps,
+                              d_status, s);
+}
+}  // namespace
+}  // extern "C++"
+
+int kite_nmpc_plant_set_params(kite_nmpc_ctx* ctx, const kite_params* params, int32_t count) {
+    if (!ctx) return KITE_EINVAL;
+    if (!params) { ctx->plant_count = 0; return KITE_OK; }
+    if (count != 1 && count != ctx->B) return KITE_EINVAL;
+    constexpr int NF = kite::kModelConstDoubles;
+    const size_t B = ctx->B;
+    if (count == 1) {                           // also a batch of one
+        ModelConst m;
+        if (!plant_params_ok(params[0], &m)) return KITE_EINVAL;
+        ctx->plant_mc1 = m;
+        ctx->plant_count = 1;
+        return KITE_OK;
+    }
+    std::vector<double> mcf((size_t)NF * B);
+    for (size_t b = 0; b < B; ++b) {
+        ModelConst m;
+        if (!plant_params_ok(params[b], &m)) return KITE_EINVAL;
+        const double* g = reinterpret_cast<const double*>(&m);
+        for (int f = 0; f < NF; ++f) mcf[(size_t)f * B + b] = g[f];
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->plant_mc) HIP_TRY(hipMalloc(&ctx->plant_mc, mcf.size() * sizeof(double)));
+    // ordered with the plant steps on the context stream, synchronous on it
+    HIP_TRY(hipMemcpyAsync(ctx->plant_mc, mcf.data(), mcf.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->plant_count = count;
+    return KITE_OK;
+}
+
+int kite_nmpc_plant_set_wind(kite_nmpc_ctx* ctx, const double* wind8) {
+    if (!ctx) return KITE_EINVAL;
+    if (!wind8) { ctx->plant_wind_mode = 0; return KITE_OK; }
+    const size_t B = ctx->B;
+    bool any = false, gust = false;
+    for (size_t b = 0; b < B; ++b)
+        for (int j = 0; j < 8; ++j) {
+            const double v = wind8[b * 8 + j];
+            if (!std::isfinite(v)) return KITE_EINVAL;
+            if (j < 6) any = any || v != 0.0;
+            if (j >= 3 && j < 6) gust = gust || v != 0.0;
+        }
+    if (!any) { ctx->plant_wind_mode = 0; return KITE_OK; }     // all zero: the reference model
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->plant_wind) HIP_TRY(hipMalloc(&ctx->plant_wind, B * 8 * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(ctx->plant_wind, wind8, B * 8 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->plant_wind_mode = gust ? 2 : 1;
+    return KITE_OK;
+}
+
+int kite_nmpc_plant_step_device(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4, double t0, double h,
+                                int32_t steps, int32_t substeps, int32_t* d_status) {
+    if (!ctx || !d_x13 || !d_u4) return KITE_EINVAL;
+    const int rc = plant_args_ok(t0, h, steps, substeps);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(plant_launch(ctx, d_x13, d_u4, t0, h, steps, substeps, d_status, ctx->stream));
+    return KITE_OK;
+}
+
+int kite_nmpc_plant_step(kite_nmpc_ctx* ctx, double* x13, const double* u4, double t0, double h, int32_t steps,
+                         int32_t substeps, int32_t* status) {
+    if (!ctx || !x13 || !u4) return KITE_EINVAL;
+    const int rc = plant_args_ok(t0, h, steps, substeps);
+    if (rc) return rc;
+    const size_t B = ctx->B;
+    // the state is advanced in place in the staging buffer; the status words
+    // (int32) sit in a scratch output and are copied out here, ahead of
+    // run_items' synchronisation
+    return run_items(ctx, {{x13, B * 13}, {u4, B * 4}}, {{nullptr, (B + 1) / 2}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         int32_t* dst = reinterpret_cast<int32_t*>(o[0]);
+                         hipError_t e = plant_launch(ctx, i[0], i[1], t0, h, steps, substeps, dst, s);
+                         if (e != hipSuccess) return e;
+                         e = hipMemcpyAsync(x13, i[0], B * 13 * sizeof(double), hipMemcpyDeviceToHost, s);
+                         if (e != hipSuccess || !status) return e;
+                         return hipMemcpyAsync(status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s);
                      });
 }
 

@@ -8,6 +8,15 @@
 //   nmpf_driver [--params yaml] [--batch B] [--steps S] [--x0 file.csv]
 //               [--ctrl-every K] [--sim-dt h] [--delay d] [--trace T] [--seed s]
 //               [--out file.jsonl] [--device i]
+//               [--plant-params file.csv] [--plant-wind file.csv]
+//
+// --plant-params (B rows of the 52 kite_params values) and --plant-wind (B rows
+// of [W0 (3) | A (3) | f_hz | phase]) give every kite a plant of its own, which
+// the controller is not told about (kite_nmpc_plant_set_params / _set_wind).
+// With either, the plant phase is one kite_nmpc_plant_step call per control
+// step (K plant steps of sim-dt inside one kernel) and the summary line gains
+// "plant_nan", the kites whose plant state went non-finite on the way to this
+// step's measurement.
 //
 // Timeline (per control step, all kites in lockstep):
 //   measure x (13 plant states) -> kite_nmpc_step (prologue predicts over
@@ -30,7 +39,7 @@ namespace {
 
 struct Args {
     std::string params = "data/umx_radian.yaml";
-    std::string x0_file, out_file;
+    std::string x0_file, out_file, plant_params_file, plant_wind_file;
     int batch = 64, steps = 100, ctrl_every = 3, trace = 1, device = 0;
     double sim_dt = 0.02, delay = 0.1;
     unsigned long long seed = 20261015ull;
@@ -39,7 +48,8 @@ struct Args {
 [[noreturn]] void usage(const char* argv0) {
     std::fprintf(stderr,
                  "usage: %s [--params yaml] [--batch B] [--steps S] [--x0 file.csv] [--ctrl-every K]\n"
-                 "          [--sim-dt h] [--delay d] [--trace T] [--seed s] [--out file.jsonl] [--device i]\n",
+                 "          [--sim-dt h] [--delay d] [--trace T] [--seed s] [--out file.jsonl] [--device i]\n"
+                 "          [--plant-params file.csv] [--plant-wind file.csv]\n",
                  argv0);
     std::exit(2);
 }
@@ -63,6 +73,8 @@ Args parse(int argc, char** argv) {
         else if (k == "--seed") a.seed = std::strtoull(val(), nullptr, 10);
         else if (k == "--out") a.out_file = val();
         else if (k == "--device") a.device = std::atoi(val());
+        else if (k == "--plant-params") a.plant_params_file = val();
+        else if (k == "--plant-wind") a.plant_wind_file = val();
         else usage(argv[0]);
     }
     if (a.batch < 1 || a.steps < 0 || a.ctrl_every < 1 || !(a.sim_dt > 0) || a.trace < 0) usage(argv[0]);
@@ -89,10 +101,10 @@ void synthetic_states(int B, unsigned long long seed, std::vector<double>& x) {
     }
 }
 
-bool read_csv(const std::string& path, int B, std::vector<double>& x) {
+bool read_csv(const std::string& path, int B, std::vector<double>& x, int cols = 13) {
     FILE* f = std::fopen(path.c_str(), "r");
     if (!f) return false;
-    x.assign((size_t)B * 13, 0.0);
+    x.assign((size_t)B * cols, 0.0);
     for (size_t i = 0; i < x.size(); ++i) {
         if (std::fscanf(f, " %lf ,", &x[i]) != 1) { std::fclose(f); return false; }
     }
@@ -126,6 +138,31 @@ int main(int argc, char** argv) {
     kite_nmpc_ctx* ctx = nullptr;
     rc = kite_nmpc_create(&kp, &cfg, B, &ctx);
     if (rc) return fail("create", rc);
+
+    // a plant of its own (model, wind, gust per kite) instead of the controller's model
+    const bool own_plant = !a.plant_params_file.empty() || !a.plant_wind_file.empty();
+    if (!a.plant_params_file.empty()) {
+        static_assert(sizeof(kite_params) == 52 * sizeof(double), "kite_params holds 52 doubles");
+        std::vector<double> pp;
+        if (!read_csv(a.plant_params_file, B, pp, 52)) {
+            std::fprintf(stderr, "nmpf_driver: cannot read %s\n", a.plant_params_file.c_str());
+            return 1;
+        }
+        std::vector<kite_params> kps(B);
+        std::memcpy(kps.data(), pp.data(), pp.size() * sizeof(double));
+        rc = kite_nmpc_plant_set_params(ctx, kps.data(), B);
+        if (rc) return fail("plant params", rc);
+    }
+    if (!a.plant_wind_file.empty()) {
+        std::vector<double> pw;
+        if (!read_csv(a.plant_wind_file, B, pw, 8)) {
+            std::fprintf(stderr, "nmpf_driver: cannot read %s\n", a.plant_wind_file.c_str());
+            return 1;
+        }
+        rc = kite_nmpc_plant_set_wind(ctx, pw.data());
+        if (rc) return fail("plant wind", rc);
+    }
+    std::vector<int32_t> plant_status(B, 0);
 
     std::vector<double> plant;            // B x 13 plant states
     if (!a.x0_file.empty()) {
@@ -183,9 +220,15 @@ int main(int argc, char** argv) {
         std::fprintf(out,
                      "{\"type\": \"step\", \"step\": %d, \"t\": %.4f, \"comp_time_ms\": %.4f, \"pos_error_mean\": %.9g, "
                      "\"pos_error_max\": %.9g, \"vel_error_mean\": %.9g, \"virt_state_mean\": %.9g, \"nan\": %d, "
-                     "\"qp_not_converged\": %d, \"step_rejected\": %d, \"restarts\": %d}\n",
+                     "\"qp_not_converged\": %d, \"step_rejected\": %d, \"restarts\": %d",
                      s, t, ms, pe_sum / std::max(1, n_fin), pe_max, ve_sum / std::max(1, n_fin),
                      th_sum / std::max(1, n_fin), n_nan, n_nc, n_rej, n_rst);
+        if (own_plant) {
+            int n_pnan = 0;
+            for (int b = 0; b < B; ++b) n_pnan += (plant_status[b] & KITE_PLANT_NAN) != 0;
+            std::fprintf(out, ", \"plant_nan\": %d", n_pnan);
+        }
+        std::fprintf(out, "}\n");
         for (int b = 0; b < std::min(a.trace, B); ++b) {
             const double* ub = &u0[(size_t)b * 4];
             std::fprintf(out, "{\"type\": \"mpc_diagnostic\", \"kite\": %d, \"step\": %d, \"pos_error\": ", b, s);
@@ -203,6 +246,13 @@ int main(int argc, char** argv) {
         for (int b = 0; b < B; ++b) {
             std::memcpy(&u4[(size_t)b * 4], &u0[(size_t)b * 4], 3 * sizeof(double));
             u4[(size_t)b * 4 + 3] = 0.0;
+        }
+        if (own_plant) {
+            // one launch for the whole control period, from the time the step began
+            rc = kite_nmpc_plant_step(ctx, plant.data(), u4.data(), t, a.sim_dt, a.ctrl_every, 4, plant_status.data());
+            if (rc) return fail("plant", rc);
+            for (int k = 0; k < a.ctrl_every; ++k) t += a.sim_dt;
+            continue;
         }
         for (int k = 0; k < a.ctrl_every; ++k) {
             for (int b = 0; b < B; ++b) {

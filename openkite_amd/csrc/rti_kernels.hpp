@@ -111,6 +111,18 @@ hipError_t launch_jacobian(const ModelConst& P, int count, const double* x, cons
                            double* Ju, hipStream_t s);
 hipError_t launch_predict(const ModelConst& P, int count, const double* x, const double* u, double h,
                           int steps, double* xo, hipStream_t s);
+// Plant simulator (plant_kernels.hip): x13 (B x 13) advanced in place over
+// steps * substeps RK4 substeps of hs from t0 under the held u4 (B x 4).
+//   mcf    per-kite model constants, field-major [kModelConstDoubles][B], or
+//          nullptr: every kite takes P (kernel argument)
+//   wind8  B x 8 [W0 (3) | A (3) | f_hz | phase], read for wind_mode 1
+//          (constant wind, A ignored) and 2 (gust); mode 0: no wind
+//   status B words (nullable), KITE_PLANT_NAN per kite, written on every call
+constexpr int kModelConstDoubles = (int)(sizeof(ModelConst) / sizeof(double));
+static_assert(sizeof(ModelConst) == kModelConstDoubles * sizeof(double), "ModelConst holds doubles only");
+hipError_t launch_plant(const ModelConst& P, const double* mcf, int B, int wind_mode, const double* wind8,
+                        double* x13, const double* u4, double t0, double hs, int steps, int substeps,
+                        int32_t* status, hipStream_t s);
 hipError_t launch_rk4_sens_items(const ModelConst& P, int sens_fp32, int count, int M, double h, const double* x,
                                  const double* u, double* xo, double* A, double* Bm, double* X2, double* AB,
                                  double* DEF, hipStream_t s);

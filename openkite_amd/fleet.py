@@ -18,6 +18,11 @@ One step of a fleet of kites on one rank:
          attitude are the next EKF measurement.  With ``noise`` (a
          ``MeasurementNoise``) that state is disturbed before it is measured:
          the controller's model no longer predicts the plant exactly.
+         With ``plant`` (a ``GpuPlant``) the kite is a simulator of its own:
+         the loop carries the true 13 kite states and a time, advances them
+         over dt under u(t0) with the plant's own parameters, wind and gust
+         (kite_nmpc_plant_step_device), and measures that state; theta and
+         thetadot still come from the plan's node 1 (nmpf_node.cpp:220).
 
 The stepper does the arithmetic; ``GpuStepper`` drives libkite_nmpc.so on
 device tensors.  Tests plug a CPU oracle stepper into the same loop to check
@@ -25,6 +30,7 @@ the sharded multi-rank flow against the unsharded batch.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import numpy as np
@@ -48,6 +54,22 @@ class GpuStepper:
     def ekf(self, dt, xe, u3, P, z, W, V):
         self.ctx.ekf_step_device(xe.shape[0], dt, xe.data_ptr(), u3.data_ptr(), P.data_ptr(),
                                  z.data_ptr() if z is not None else 0, W.data_ptr(), V.data_ptr())
+
+
+class GpuPlant:
+    """The batched plant simulator of one C-ABI context on device tensors
+    (kite_nmpc_plant_step_device: the context's plant parameters, wind and gust,
+    see ``BatchNMPC.plant_set_params`` / ``plant_set_wind``): ``steps`` plant
+    steps of ``h`` per control period, RK4 with ``substeps`` each."""
+
+    def __init__(self, ctx, h: float = 0.02, steps: int = 1, substeps: int = 4):
+        self.ctx, self.h, self.steps, self.substeps = ctx, float(h), int(steps), int(substeps)
+
+    def advance(self, x13, u0, t0, status):
+        """x13 (B, 13) in place from t0 over steps * h under the held u0 (B, 4);
+        status (B,) int32 receives the KITE_PLANT_* words."""
+        self.ctx.plant_step_device(x13.data_ptr(), u0.data_ptr(), t0, self.h, self.steps, self.substeps,
+                                   status.data_ptr())
 
 
 class MeasurementNoise:
@@ -81,7 +103,8 @@ class FleetLoop:
     """Closed-loop state of one rank's shard and its per-step sequence."""
 
     def __init__(self, stepper, x0: torch.Tensor, N: int, dt: float, ekf: bool = False, ekf_substeps: int = 5,
-                 covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None):
+                 covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None,
+                 plant=None):
         B = x0.shape[0]
         dev = x0.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -106,6 +129,15 @@ class FleetLoop:
             self.u3 = torch.zeros((B, 3), **f64)
             self.z = self.x0[:, 6:13].clone()
         self.gathered = None
+        # a plant of its own (``GpuPlant``, or any object with h, steps and
+        # advance): the loop carries the true kite state xp and the time t
+        self.plant = plant
+        if plant is not None:
+            if not math.isclose(plant.steps * plant.h, dt, rel_tol=1e-12, abs_tol=0.0):
+                raise ValueError(f"plant: steps * h = {plant.steps * plant.h} is not the control period dt = {dt}")
+            self.xp = x0[:, :13].clone().contiguous()
+            self.t = 0.0
+            self.plant_status = torch.zeros((B,), dtype=torch.int32, device=dev)
 
     def restart(self):
         """Start the next episode: every kite back at its launch state, the
@@ -114,6 +146,10 @@ class FleetLoop:
         self.stepper.reset()
         self.x0.copy_(self.x_init)
         self.u0.zero_()
+        if self.plant is not None:
+            self.xp.copy_(self.x_init[:, :13])
+            self.t = 0.0
+            self.plant_status.zero_()
         if self.ekf:
             self.xe.copy_(self.x_init[:, :13])
             self.P.copy_(self.P_init)
@@ -132,7 +168,15 @@ class FleetLoop:
         self.stepper.rti(self.x0, self.u0, self.traj, self.diag, self.status)
         if self.pub is not None:
             self.gathered = self.pub.publish(self.u0, self.diag)
-        self.x0.copy_(self.traj[:, 1, :])
+        if self.plant is None:
+            self.x0.copy_(self.traj[:, 1, :])
+        else:
+            # the kite flies on under u(t0); it is measured at t0 + dt, theta and
+            # thetadot come from the plan (nmpf_node.cpp:220)
+            self.plant.advance(self.xp, self.u0, self.t, self.plant_status)
+            self.t += self.dt
+            self.x0[:, :13].copy_(self.xp)
+            self.x0[:, 13:].copy_(self.traj[:, 1, 13:])
         if self.noise is not None:
             self.noise.apply(self.x0)
         if self.ekf:

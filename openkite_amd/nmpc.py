@@ -23,6 +23,7 @@ DEFAULT_PARAMS = os.path.join(REPO, "data", "umx_radian.yaml")
 KITE_OK, KITE_EINVAL, KITE_EHIP, KITE_ENOMEM, KITE_ENODEV, KITE_EIO, KITE_EPARSE, KITE_ESTATE = 0, -1, -2, -3, -4, -5, -6, -7
 ST_NAN, ST_QP_NOT_CONV, ST_MIN_SPEED, ST_STATE_BOUND, ST_THETA_WRAP, ST_STEP_REJECTED = 1, 2, 4, 8, 16, 32
 ST_RESTART = 64
+PLANT_NAN = 1                      # KITE_PLANT_NAN (plant status word)
 
 _PARAM_FIELDS = ["b", "c", "AR", "S", "lam", "St", "lt", "Sf", "lf", "Xac",
                  "mass", "Ixx", "Iyy", "Izz", "Ixz",
@@ -168,6 +169,13 @@ _SIGNATURES = {
     "kite_nmpc_ekf_step_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
+    "kite_nmpc_plant_set_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
+    "kite_nmpc_plant_set_wind": (ctypes.c_int, [ctypes.c_void_p, _DP]),
+    "kite_nmpc_plant_step": (ctypes.c_int, [ctypes.c_void_p, _DP, _DP, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_int32, ctypes.c_int32, _IP]),
+    "kite_nmpc_plant_step_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.c_void_p]),
 }
 
 
@@ -225,6 +233,29 @@ def load_properties(path: str = DEFAULT_PARAMS) -> KiteParams:
     p = KiteParams()
     _check(lib().kite_params_load_yaml(path.encode(), ctypes.byref(p)), f"load {path}")
     return p
+
+
+# perturb_params' default selection: what differs between two airframes of one
+# design (mass, inertias, aerodynamic coefficients); the geometry (b .. Xac) and
+# the tether (Lt .. rz) stay as they are
+PERTURB_FIELDS = _PARAM_FIELDS[_PARAM_FIELDS.index("mass"):_PARAM_FIELDS.index("CDde") + 1]
+
+
+def perturb_params(params, B: int, rel: float, seed: int, fields=None) -> np.ndarray:
+    """A seeded fleet of B plant models around ``params`` (a ``KiteParams`` or
+    its 52 values) for ``BatchNMPC.plant_set_params``: a (B, 52) array in which
+    every selected field is multiplied by 1 + rel * U(-1, 1), one draw per kite
+    and field from ``numpy.random.default_rng(seed)``.  fields: names from
+    ``KiteParams`` (default ``PERTURB_FIELDS``); the others are copied."""
+    base = params.as_array() if isinstance(params, KiteParams) else _f64(params).reshape(-1)
+    if base.size != len(_PARAM_FIELDS):
+        raise ValueError("52 parameter values expected")
+    names = PERTURB_FIELDS if fields is None else list(fields)
+    cols = [_PARAM_FIELDS.index(f) for f in names]      # ValueError on an unknown name
+    out = np.repeat(base[None, :], int(B), axis=0)
+    draws = np.random.default_rng(seed).uniform(-1.0, 1.0, size=(int(B), len(cols)))
+    out[:, cols] *= 1.0 + float(rel) * draws
+    return out
 
 
 def resolve_qp_kernel(qp_kernel: int, N: int) -> int:
@@ -445,6 +476,64 @@ class BatchNMPC:
         xo = np.zeros_like(x)
         _check(lib().kite_nmpc_predict(self._h, x.shape[0], _p(x), _p(u), float(tf), int(steps), _p(xo)), "predict")
         return xo
+
+    # --- plant simulator --------------------------------------------------------
+    def plant_set_params(self, params=None):
+        """The plant's model (kite_nmpc_plant_set_params): None = the
+        controller's own parameters, one ``KiteParams`` (or 52 values) = one
+        plant model for every kite, a (B, 52) array = a model per kite (see
+        ``perturb_params``)."""
+        if params is None:
+            _check(lib().kite_nmpc_plant_set_params(self._h, None, 0), "plant_set_params")
+            return
+        if isinstance(params, KiteParams):
+            params = params.as_array()
+        p = _f64(params)
+        if p.ndim == 1:
+            p = p.reshape(1, -1)
+        if p.ndim != 2 or p.shape[1] != len(_PARAM_FIELDS):
+            raise ValueError("plant parameters: 52 values per kite")
+        _check(lib().kite_nmpc_plant_set_params(self._h, ctypes.c_void_p(p.ctypes.data), p.shape[0]),
+               "plant_set_params")
+
+    def plant_set_wind(self, wind=None, gust_amp=None, gust_hz=None, gust_phase=None):
+        """The wind the plant sees (kite_nmpc_plant_set_wind), world frame, m/s:
+        W(t) = wind + gust_amp sin(2 pi gust_hz t + gust_phase) per kite.  wind
+        and gust_amp are (B, 3) or (3,), gust_hz and gust_phase (B,) or scalars;
+        omitted parts are zero, all omitted = no wind.  The controller's model
+        is not told (that is ``set_wind``)."""
+        if wind is None and gust_amp is None and gust_hz is None and gust_phase is None:
+            _check(lib().kite_nmpc_plant_set_wind(self._h, None), "plant_set_wind")
+            return
+        B = self.batch
+        w8 = np.zeros((B, 8))
+        if wind is not None:
+            w8[:, 0:3] = np.broadcast_to(np.asarray(wind, dtype=np.float64), (B, 3))
+        if gust_amp is not None:
+            w8[:, 3:6] = np.broadcast_to(np.asarray(gust_amp, dtype=np.float64), (B, 3))
+        if gust_hz is not None:
+            w8[:, 6] = np.broadcast_to(np.asarray(gust_hz, dtype=np.float64), (B,))
+        if gust_phase is not None:
+            w8[:, 7] = np.broadcast_to(np.asarray(gust_phase, dtype=np.float64), (B,))
+        _check(lib().kite_nmpc_plant_set_wind(self._h, _p(w8)), "plant_set_wind")
+
+    def plant_step(self, x13, u4, t0: float, h: float, steps: int = 1, substeps: int = 4):
+        """Advance the (B, 13) plant states from t0 over steps * h under the held
+        control u4 (B, 4), RK4 with `substeps` per step; returns (x13, status),
+        status the KITE_PLANT_* words (``PLANT_NAN``)."""
+        x = _f64(x13).reshape(self.batch, 13).copy()
+        u = _f64(u4).reshape(self.batch, 4)
+        st = np.zeros(self.batch, dtype=np.int32)
+        _check(lib().kite_nmpc_plant_step(self._h, _p(x), _p(u), float(t0), float(h), int(steps), int(substeps),
+                                          st.ctypes.data_as(_IP)), "plant_step")
+        return x, st
+
+    def plant_step_device(self, x13_ptr: int, u4_ptr: int, t0: float, h: float, steps: int = 1, substeps: int = 4,
+                          status_ptr: int = 0):
+        """plant_step in place on device pointers (asynchronous on the context stream)."""
+        v = lambda p: ctypes.c_void_p(p) if p else None
+        _check(lib().kite_nmpc_plant_step_device(self._h, v(x13_ptr), v(u4_ptr), float(t0), float(h), int(steps),
+                                                 int(substeps), v(status_ptr)), "plant_step_device")
 
     def rk4_sens(self, x15, u4, tf: float, M: int):
         x = _f64(x15).reshape(-1, 15); u = _f64(u4).reshape(-1, 4)
