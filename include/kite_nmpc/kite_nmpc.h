@@ -48,7 +48,9 @@ extern "C" {
                                       additive, no version change: the plant
                                       simulator (kite_nmpc_plant_set_params,
                                       _plant_set_wind, _plant_step, _plant_step_device,
-                                      KITE_PLANT_NAN)                             */
+                                      KITE_PLANT_NAN) and the wind-estimating EKF
+                                      (kite_nmpc_windekf_step[_device], _jacobian_wind,
+                                      _set_wind_device, KITE_EKF_*)               */
 #define KITE_PATH_MAX_HARMONICS 8 /* Fourier path: harmonics per axis              */
 
 /* ---- error codes ------------------------------------------------------ */
@@ -357,6 +359,47 @@ int kite_nmpc_ekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, double* x13
 int kite_nmpc_ekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, double* d_x13,
                               const double* d_u3, double* d_P169, const double* d_z7,
                               const double* d_W169, const double* d_V49);
+
+/* ---- wind-estimating EKF (build extension; additive, no version change) ---
+ * The filter above with the world-frame wind W (m/s, a random walk) as three
+ * more states: x16 = [x13 | W3], P256 count x 16 x 16 row-major, H = [0_{7x6}
+ * I_7 0_{7x3}].  One call runs `substeps` propagations of dt / substeps (one
+ * RK4 step of the wind model under the estimated wind, A = I + J h with
+ * J = [df/dx | df/dW; 0], P = A P A' + W256) and, when z7 != NULL, one update
+ * as kite_nmpc_ekf_step does it, after which P is made exactly symmetric
+ * ((P + P') / 2: the update alone lets rounding asymmetry grow from period
+ * to period).  x16 and P256 are updated in place; W256 /
+ * V49 are shared by all kites.  status (count words, nullable) receives the
+ * KITE_EKF_* bits, written (not OR-ed) on every call.  count < 1, dt <= 0 or
+ * non-finite, substeps < 1 or > 2^24: KITE_EINVAL.                          */
+#define KITE_EKF_NAN      1  /* estimate or P non-finite (on entry or in a substep):
+                                the kite keeps its last finite x16 and P        */
+#define KITE_EKF_S_NOT_PD 2  /* a pivot of S = H P H' + V was <= 0 or non-finite:
+                                the update is skipped, the propagated estimate kept */
+/* 13-state block and V: kite_ekf_default_covariances; wind block: 1e-4
+ * (m/s)^2 per propagation on W256's diagonal, 25 (m/s)^2 on P0's.           */
+void kite_windekf_default_covariances(double* W256, double* V49, double* P0_256);
+int kite_nmpc_windekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, double* x16,
+                           const double* u3, double* P256, const double* z7, const double* W256,
+                           const double* V49, int32_t* status);
+/* Same on device pointers, asynchronous on the context stream.              */
+int kite_nmpc_windekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps,
+                                  double* d_x16, const double* d_u3, double* d_P256, const double* d_z7,
+                                  const double* d_W256, const double* d_V49, int32_t* d_status);
+/* The filter's Jacobian pass: J (count x 13 x 16, row-major) = [df/dx | df/dW]
+ * of the wind model at (x13, u3) under the winds w3 (count x 3).            */
+int kite_nmpc_jacobian_wind(kite_nmpc_ctx* ctx, int32_t count, const double* x13, const double* u3,
+                            const double* w3, double* J);
+/* kite_nmpc_set_wind from device memory, asynchronous on the context stream:
+ * the B winds sit `stride` doubles apart at d_wind (stride >= 3; 16 when
+ * d_wind points at column 13 of an x16 array).  Each component is clamped to
+ * +-wmax and a non-finite one replaced by 0 (the device cannot refuse bad
+ * values as the host entry does).  Switches the wind model on -- also for
+ * all-zero winds -- and re-captures the step graph only when that switch
+ * changes, not on a refresh of the values; kite_nmpc_set_wind(ctx, NULL)
+ * returns to the reference model.  wmax <= 0 or non-finite, stride < 3:
+ * KITE_EINVAL.                                                              */
+int kite_nmpc_set_wind_device(kite_nmpc_ctx* ctx, const double* d_wind, int32_t stride, double wmax);
 
 /* Per-kernel device time [ms] of the last step (cfg.timing = 1):
  * [prologue, rk4_sens, condense, qp, total, qp_main]; qp is the whole QP

@@ -247,11 +247,16 @@ __host__ __device__ __forceinline__ V3<T> rot_world(T w, const V3<T>& u, T ww_uu
 // pressure, the rate-damping terms -- see the air-relative body velocity
 // v_a = v - q^-1 (x) [0,W] (x) q, while gravity, the tether and the kinematics
 // keep the inertial v.  WIND = false is the reference model, instruction for
-// instruction.
+// instruction.  WT is the wind's scalar type: double (the default) where the
+// wind is a constant of the prediction, T = Dual where it is differentiated
+// (the wind-estimating filter's d f / d W, windekf_kernels.hip, which names it:
+// kite_rhs<Dual, true, Dual>; it is never deduced from the argument); the
+// arithmetic and its order are the same.
 // ---------------------------------------------------------------------------
-template <class T, bool WIND = false>
+template <class WT> struct WindArg { using ptr = const WT*; };
+template <class T, bool WIND = false, class WT = double>
 __host__ __device__ __forceinline__ void kite_rhs(const ModelConst& P, const T* x, const T* u, T* f,
-                                                  const double* wnd = nullptr) {
+                                                  typename WindArg<WT>::ptr wnd = nullptr) {
     const V3<T> v{x[0], x[1], x[2]};
     const V3<T> w{x[3], x[4], x[5]};
     const V3<T> r{x[6], x[7], x[8]};
@@ -260,10 +265,10 @@ __host__ __device__ __forceinline__ void kite_rhs(const ModelConst& P, const T* 
     const T thr = u[0], dE = u[1], dR = u[2];
     V3<T> va = v;
     if constexpr (WIND) {
-        // the wind is a constant: its rotation multiplies by plain doubles
-        // (a dual-typed constant would carry zero tangents through every product)
+        // the wind is a constant (WT = double): its rotation multiplies by plain
+        // doubles (a dual-typed constant would carry zero tangents through every product)
         const T wwuu = qw * qw - dot3(qu, qu);
-        const double W0 = wnd[0], W1 = wnd[1], W2 = wnd[2];
+        const WT W0 = wnd[0], W1 = wnd[1], W2 = wnd[2];
         const T uv2 = 2.0 * (qu.x * W0 + qu.y * W1 + qu.z * W2);
         const T cx = qu.y * W2 - qu.z * W1, cy = qu.z * W0 - qu.x * W2, cz = qu.x * W1 - qu.y * W0;
         const T w2 = 2.0 * qw;

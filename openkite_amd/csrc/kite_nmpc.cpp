@@ -1162,6 +1162,101 @@ int kite_nmpc_ekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, double* x13
     return KITE_OK;
 }
 
+// ---- wind-estimating EKF (windekf_kernels.hip) ------------------------------
+void kite_windekf_default_covariances(double* W256, double* V49, double* P0_256) {
+    // 13-state block and V: kiteEKF.cpp's defaults; wind block (a random walk):
+    // 1e-4 (m/s)^2 per propagation, 25 (m/s)^2 initially (a 5 m/s prior: DESIGN 4.8)
+    double W13[169], P13[169];
+    kite_ekf_default_covariances(W13, V49, P13);
+    for (int i = 0; i < 256; ++i) {
+        if (W256) W256[i] = 0.0;
+        if (P0_256) P0_256[i] = 0.0;
+    }
+    for (int i = 0; i < 13; ++i)
+        for (int j = 0; j < 13; ++j) {
+            if (W256) W256[i * 16 + j] = W13[i * 13 + j];
+            if (P0_256) P0_256[i * 16 + j] = P13[i * 13 + j];
+        }
+    for (int i = 13; i < 16; ++i) {
+        if (W256) W256[i * 16 + i] = 1e-4;
+        if (P0_256) P0_256[i * 16 + i] = 25.0;
+    }
+}
+
+extern "C++" {
+namespace {
+int windekf_args_ok(int32_t count, double dt, int32_t substeps) {
+    if (count < 1 || !std::isfinite(dt) || !(dt > 0.0)) return KITE_EINVAL;
+    if (substeps < 1 || substeps > (1 << 24)) return KITE_EINVAL;
+    return KITE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int kite_nmpc_windekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, double* d_x16,
+                                  const double* d_u3, double* d_P256, const double* d_z7, const double* d_W256,
+                                  const double* d_V49, int32_t* d_status) {
+    if (!ctx || !d_x16 || !d_u3 || !d_P256 || !d_W256 || (d_z7 && !d_V49)) return KITE_EINVAL;
+    const int rc = windekf_args_ok(count, dt, substeps);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(kite::launch_ekf_wind(ctx->mc, count, dt, substeps, d_x16, d_u3, d_P256, d_z7, d_W256, d_V49, d_status,
+                                  ctx->stream));
+    return KITE_OK;
+}
+
+int kite_nmpc_windekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, double* x16,
+                           const double* u3, double* P256, const double* z7, const double* W256, const double* V49,
+                           int32_t* status) {
+    if (!ctx || !x16 || !u3 || !P256 || !W256 || (z7 && !V49)) return KITE_EINVAL;
+    const int rc0 = windekf_args_ok(count, dt, substeps);
+    if (rc0) return rc0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t c = count;
+    const size_t nx = c * 16, nu = c * 3, np = c * 256, nz = z7 ? c * 7 : 0, ns = (c + 1) / 2;
+    int rc = ensure_scratch(ctx, (nx + nu + np + nz + 256 + 49 + ns) * sizeof(double));
+    if (rc) return rc;
+    double *dx = ctx->scratch, *du = dx + nx, *dP = du + nu, *dz = dP + np, *dW = dz + nz, *dV = dW + 256;
+    int32_t* dst = reinterpret_cast<int32_t*>(dV + 49);
+    hipStream_t s = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dx, x16, nx * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(du, u3, nu * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dP, P256, np * sizeof(double), hipMemcpyHostToDevice, s));
+    if (z7) HIP_TRY(hipMemcpyAsync(dz, z7, nz * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dW, W256, 256 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (V49) HIP_TRY(hipMemcpyAsync(dV, V49, 49 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(kite::launch_ekf_wind(ctx->mc, count, dt, substeps, dx, du, dP, z7 ? dz : nullptr, dW, dV, dst, s));
+    HIP_TRY(hipMemcpyAsync(x16, dx, nx * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(P256, dP, np * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return KITE_OK;
+}
+
+int kite_nmpc_jacobian_wind(kite_nmpc_ctx* ctx, int32_t count, const double* x13, const double* u3, const double* w3,
+                            double* J) {
+    if (!ctx || count < 1 || !x13 || !u3 || !w3 || !J) return KITE_EINVAL;
+    const size_t c = count;
+    return run_items(ctx, {{x13, c * 13}, {u3, c * 3}, {w3, c * 3}}, {{J, c * 13 * 16}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         return kite::launch_jacobian_wind(ctx->mc, count, i[0], i[1], i[2], o[0], s);
+                     });
+}
+
+int kite_nmpc_set_wind_device(kite_nmpc_ctx* ctx, const double* d_wind, int32_t stride, double wmax) {
+    if (!ctx || !d_wind || stride < 3 || !std::isfinite(wmax) || !(wmax > 0.0)) return KITE_EINVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->wind) HIP_TRY(hipMalloc(&ctx->wind, (size_t)ctx->B * 3 * sizeof(double)));
+    HIP_TRY(kite::launch_wind_copy(ctx->B, d_wind, stride, wmax, ctx->wind, ctx->stream));
+    // the captured step reads ctx->wind when it runs: a refresh of the values
+    // needs no new graph, only the switch to the WIND kernels does
+    if (!ctx->has_wind) {
+        ctx->has_wind = true;
+        ++ctx->graph_gen;
+    }
+    return KITE_OK;
+}
+
 int kite_nmpc_rk4_sens(kite_nmpc_ctx* ctx, int32_t count, const double* x15, const double* u4, double tf,
                        int32_t M, double* xnext, double* A, double* Bm) {
     if (!ctx || count < 1 || !x15 || !u4 || !xnext || !A || !Bm || M < 1 || !std::isfinite(tf)) return KITE_EINVAL;

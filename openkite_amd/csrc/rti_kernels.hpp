@@ -144,5 +144,17 @@ hipError_t launch_colloc(const ModelConst& P, const CollocConst& C, int count, c
 // batched EKF propagate (+ update when z != nullptr), in place on x and Pc (ekf_kernels.hip)
 hipError_t launch_ekf(const ModelConst& P, int count, double dt, double* x, const double* u, double* Pc,
                       const double* z, const double* W, const double* V, hipStream_t s);
+// Wind-estimating EKF (windekf_kernels.hip): `substeps` propagations of
+// dt / substeps (+ one update when z != nullptr), in place on x16 (count x 16,
+// [x13 | W3]) and Pc (count x 16 x 16); status: count words (nullable),
+// KITE_EKF_* per kite, written on every call
+hipError_t launch_ekf_wind(const ModelConst& P, int count, double dt, int substeps, double* x16, const double* u,
+                           double* Pc, const double* z, const double* W, const double* V, int32_t* status,
+                           hipStream_t s);
+// J (count x 13 x 16) = [df/dx | df/dW] under the winds w (count x 3)
+hipError_t launch_jacobian_wind(const ModelConst& P, int count, const double* x, const double* u, const double* w,
+                                double* J, hipStream_t s);
+// dst (B x 3) <- B winds `stride` doubles apart at src, clamped to +-wmax, non-finite -> 0
+hipError_t launch_wind_copy(int B, const double* src, int stride, double wmax, double* dst, hipStream_t s);
 
 }  // namespace kite

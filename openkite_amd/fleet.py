@@ -6,7 +6,10 @@ One step of a fleet of kites on one rank:
          estimate under the control applied last, in `ekf_substeps` RK4 steps
          of dt/ekf_substeps, and update it with the measured position +
          attitude (z, 7 values) on the last one; the RTI starts from the
-         estimate.
+         estimate.  With ``wind_ekf`` instead: the filter that carries the
+         wind as three more states (kite_nmpc_windekf_step_device), the same
+         propagation and update in one launch, after which the estimated wind
+         becomes the wind of the RTI's model (kite_nmpc_set_wind_device).
   RTI    one real-time iteration of the NMPC for every kite of the shard
          (kite_nmpc_step_device: KiteNMPF::computeControl, kiteNMPF.cpp:199-316).
   pub    optional publish of u0 + mpc_diagnostic of every kite to every rank
@@ -54,6 +57,18 @@ class GpuStepper:
     def ekf(self, dt, xe, u3, P, z, W, V):
         self.ctx.ekf_step_device(xe.shape[0], dt, xe.data_ptr(), u3.data_ptr(), P.data_ptr(),
                                  z.data_ptr() if z is not None else 0, W.data_ptr(), V.data_ptr())
+
+    def wind_ekf(self, dt, substeps, xe, u3, P, z, W, V, status):
+        """One fused step of the wind-estimating EKF on xe (B, 16) and P (B, 16, 16)."""
+        self.ctx.wind_ekf_step_device(xe.shape[0], dt, substeps, xe.data_ptr(), u3.data_ptr(), P.data_ptr(),
+                                      z.data_ptr() if z is not None else 0, W.data_ptr(), V.data_ptr(),
+                                      status.data_ptr() if status is not None else 0)
+
+    def set_wind_device(self, wind, wmax):
+        """The controller's wind from a (B, 3) view of a device tensor (rows
+        ``wind.stride(0)`` doubles apart, components contiguous)."""
+        assert wind.dtype == torch.float64 and wind.stride(1) == 1
+        self.ctx.set_wind_device(wind.data_ptr(), wind.stride(0), wmax)
 
 
 class GpuPlant:
@@ -104,7 +119,9 @@ class FleetLoop:
 
     def __init__(self, stepper, x0: torch.Tensor, N: int, dt: float, ekf: bool = False, ekf_substeps: int = 5,
                  covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None,
-                 plant=None):
+                 plant=None, wind_ekf: bool = False, wind_max: float = 20.0):
+        if ekf and wind_ekf:
+            raise ValueError("ekf and wind_ekf are two estimators: choose one")
         B = x0.shape[0]
         dev = x0.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -128,6 +145,27 @@ class FleetLoop:
             self.xe = self.x0[:, :13].clone()
             self.u3 = torch.zeros((B, 3), **f64)
             self.z = self.x0[:, 6:13].clone()
+        # the wind-estimating EKF: xe = [x13 | W3] (the wind estimate starts at
+        # 0), P 16 x 16; one fused call per step, then the estimated wind goes
+        # to the controller's model on the device
+        self.wind_ekf = wind_ekf
+        self.wind_max = float(wind_max)
+        if wind_ekf:
+            if covariances is None:
+                raise ValueError("the wind EKF needs (W, V, P0) in the 16-state shapes")
+            W, V, P0 = (np.asarray(a, dtype=np.float64) for a in covariances)
+            if W.shape != (16, 16) or V.shape != (7, 7) or P0.shape != (16, 16):
+                raise ValueError("the wind EKF needs W (16, 16), V (7, 7), P0 (16, 16)")
+            self.W = torch.from_numpy(W.copy()).to(dev)
+            self.V = torch.from_numpy(V.copy()).to(dev)
+            self.P = torch.from_numpy(np.repeat(P0[None], B, axis=0)).to(dev)
+            self.P_init = self.P.clone()
+            self.xe = torch.zeros((B, 16), **f64)
+            self.xe[:, :13].copy_(self.x0[:, :13])
+            self.u3 = torch.zeros((B, 3), **f64)
+            self.z = self.x0[:, 6:13].clone()
+            self.ekf_status = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self.wind_ekf_fresh = True
         self.gathered = None
         # a plant of its own (``GpuPlant``, or any object with h, steps and
         # advance): the loop carries the true kite state xp and the time t
@@ -154,8 +192,31 @@ class FleetLoop:
             self.xe.copy_(self.x_init[:, :13])
             self.P.copy_(self.P_init)
             self.z.copy_(self.x_init[:, 6:13])
+        if self.wind_ekf:
+            self.xe.zero_()
+            self.xe[:, :13].copy_(self.x_init[:, :13])
+            self.P.copy_(self.P_init)
+            self.z.copy_(self.x_init[:, 6:13])
+            self.ekf_status.zero_()
+            self.wind_ekf_fresh = True
 
     def step(self):
+        if self.wind_ekf:
+            # the same propagation and update in one launch; the wind it
+            # estimates is what the RTI's predictions assume from this step
+            # on.  The first step of an episode has nothing to filter: xe is the
+            # state measured at this instant, no time has passed under any
+            # control.  (A propagation over dt followed by that stale
+            # measurement is a position innovation of dt * v, which a filter
+            # with a wind state books as several m/s of wind.)
+            if self.wind_ekf_fresh:
+                self.wind_ekf_fresh = False
+            else:
+                self.u3.copy_(self.u0[:, :3])
+                self.stepper.wind_ekf(self.dt, self.ekf_substeps, self.xe, self.u3, self.P, self.z, self.W, self.V,
+                                      self.ekf_status)
+            self.stepper.set_wind_device(self.xe[:, 13:], self.wind_max)
+            self.x0[:, :13].copy_(self.xe[:, :13])
         if self.ekf:
             # propagate under the control applied last (u(t0) of the previous
             # plan), update with the measurement on the last substep
@@ -179,5 +240,5 @@ class FleetLoop:
             self.x0[:, 13:].copy_(self.traj[:, 1, 13:])
         if self.noise is not None:
             self.noise.apply(self.x0)
-        if self.ekf:
+        if self.ekf or self.wind_ekf:
             self.z.copy_(self.x0[:, 6:13])

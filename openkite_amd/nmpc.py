@@ -24,6 +24,8 @@ KITE_OK, KITE_EINVAL, KITE_EHIP, KITE_ENOMEM, KITE_ENODEV, KITE_EIO, KITE_EPARSE
 ST_NAN, ST_QP_NOT_CONV, ST_MIN_SPEED, ST_STATE_BOUND, ST_THETA_WRAP, ST_STEP_REJECTED = 1, 2, 4, 8, 16, 32
 ST_RESTART = 64
 PLANT_NAN = 1                      # KITE_PLANT_NAN (plant status word)
+EKF_NAN, EKF_S_NOT_PD = 1, 2       # KITE_EKF_* (status word of the wind-estimating EKF)
+WIND_MAX_DEFAULT = 20.0            # set_wind_device: clamp of an estimated wind component, m/s
 
 _PARAM_FIELDS = ["b", "c", "AR", "S", "lam", "St", "lt", "Sf", "lf", "Xac",
                  "mass", "Ixx", "Iyy", "Izz", "Ixz",
@@ -169,6 +171,15 @@ _SIGNATURES = {
     "kite_nmpc_ekf_step_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
+    "kite_windekf_default_covariances": (None, [_DP, _DP, _DP]),
+    "kite_nmpc_windekf_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _DP,
+                                              _DP, _DP, _DP, _DP, _DP, _IP]),
+    "kite_nmpc_windekf_step_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p]),
+    "kite_nmpc_jacobian_wind": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, _DP]),
+    "kite_nmpc_set_wind_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]),
     "kite_nmpc_plant_set_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "kite_nmpc_plant_set_wind": (ctypes.c_int, [ctypes.c_void_p, _DP]),
     "kite_nmpc_plant_step": (ctypes.c_int, [ctypes.c_void_p, _DP, _DP, ctypes.c_double, ctypes.c_double,
@@ -471,6 +482,49 @@ class BatchNMPC:
                "ekf_step")
         return x, Pm
 
+    def wind_ekf_step_device(self, count: int, dt: float, substeps: int, d_x16: int, d_u3: int, d_P256: int,
+                             d_z7: int, d_W256: int, d_V49: int, d_status: int = 0):
+        """Device-pointer step of the wind-estimating EKF (asynchronous on the
+        context stream): `substeps` propagations of dt / substeps and, with
+        d_z7, one update; d_status (count int32) receives the KITE_EKF_* words."""
+        _check(lib().kite_nmpc_windekf_step_device(self._h, int(count), float(dt), int(substeps), d_x16, d_u3, d_P256,
+                                                   d_z7 or None, d_W256, d_V49 or None, d_status or None),
+               "wind_ekf_step_device")
+
+    def wind_ekf_step(self, x16, u3, P, dt: float, substeps: int = 1, z7=None, W=None, V=None):
+        """Batched wind-estimating EKF (kite_nmpc_windekf_step): the state is
+        [x13 | W3], P (count, 16, 16); `substeps` propagations of dt / substeps
+        under the estimated wind, then one update when z7 is given.  Returns
+        (x16, P, status), status the KITE_EKF_* words (``EKF_NAN``,
+        ``EKF_S_NOT_PD``)."""
+        x = _f64(x16).reshape(-1, 16).copy()
+        c = x.shape[0]
+        Pm = _f64(P).reshape(c, 16, 16).copy()
+        u = _f64(u3).reshape(c, 3)
+        Wd, Vd, _ = wind_ekf_default_covariances()
+        W = Wd if W is None else _f64(W).reshape(16, 16)
+        V = Vd if V is None else _f64(V).reshape(7, 7)
+        z = None if z7 is None else _f64(z7).reshape(c, 7)
+        st = np.zeros(c, dtype=np.int32)
+        _check(lib().kite_nmpc_windekf_step(self._h, c, float(dt), int(substeps), _p(x), _p(u), _p(Pm), _p(z), _p(W),
+                                            _p(V), st.ctypes.data_as(_IP)), "wind_ekf_step")
+        return x, Pm, st
+
+    def jacobian_wind(self, x13, u3, w3):
+        """[df/dx | df/dW] (count, 13, 16) of the wind model at (x13, u3) under
+        the winds w3 (count, 3): the wind-estimating filter's Jacobian pass."""
+        x = _f64(x13).reshape(-1, 13); u = _f64(u3).reshape(-1, 3); w = _f64(w3).reshape(-1, 3)
+        J = np.zeros((x.shape[0], 13, 16))
+        _check(lib().kite_nmpc_jacobian_wind(self._h, x.shape[0], _p(x), _p(u), _p(w), _p(J)), "jacobian_wind")
+        return J
+
+    def set_wind_device(self, ptr: int, stride: int = 3, wmax: float = WIND_MAX_DEFAULT):
+        """``set_wind`` from device memory (kite_nmpc_set_wind_device,
+        asynchronous on the context stream): B winds `stride` doubles apart at
+        ptr, each component clamped to +-wmax, a non-finite one replaced by 0."""
+        _check(lib().kite_nmpc_set_wind_device(self._h, ctypes.c_void_p(ptr) if ptr else None, int(stride),
+                                               float(wmax)), "set_wind_device")
+
     def predict(self, x15, u4, tf: float, steps: int = 1):
         x = _f64(x15).reshape(-1, 15); u = _f64(u4).reshape(-1, 4)
         xo = np.zeros_like(x)
@@ -586,6 +640,15 @@ def ekf_default_covariances():
     """(W, V, P0) of KiteEKF (kiteEKF.cpp:6-13, P0 = 10 W at :26)."""
     W = np.zeros((13, 13)); V = np.zeros((7, 7)); P0 = np.zeros((13, 13))
     lib().kite_ekf_default_covariances(_p(W), _p(V), _p(P0))
+    return W, V, P0
+
+
+def wind_ekf_default_covariances():
+    """(W, V, P0) of the wind-estimating EKF, 16 x 16 / 7 x 7 / 16 x 16: the
+    ``ekf_default_covariances`` blocks and the wind block of
+    kite_windekf_default_covariances."""
+    W = np.zeros((16, 16)); V = np.zeros((7, 7)); P0 = np.zeros((16, 16))
+    lib().kite_windekf_default_covariances(_p(W), _p(V), _p(P0))
     return W, V, P0
 
 
