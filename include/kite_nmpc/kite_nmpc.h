@@ -50,7 +50,9 @@ extern "C" {
                                       _plant_set_wind, _plant_step, _plant_step_device,
                                       KITE_PLANT_NAN) and the wind-estimating EKF
                                       (kite_nmpc_windekf_step[_device], _jacobian_wind,
-                                      _set_wind_device, KITE_EKF_*)               */
+                                      _set_wind_device, KITE_EKF_*) and the parameter
+                                      identification (kite_nmpc_identify[_device],
+                                      _ident_normal, _ident_sens, KITE_IDENT_*)   */
 #define KITE_PATH_MAX_HARMONICS 8 /* Fourier path: harmonics per axis              */
 
 /* ---- error codes ------------------------------------------------------ */
@@ -400,6 +402,95 @@ int kite_nmpc_jacobian_wind(kite_nmpc_ctx* ctx, int32_t count, const double* x13
  * returns to the reference model.  wmax <= 0 or non-finite, stride < 3:
  * KITE_EINVAL.                                                              */
 int kite_nmpc_set_wind_device(kite_nmpc_ctx* ctx, const double* d_wind, int32_t stride, double wmax);
+
+/* ---- aerodynamic parameter identification (additive, no version change) ----
+ * src/kite_control/kite_identification_test.cpp: fit the 21 aerodynamic
+ * coefficients of a kite to a logged flight, batched over `count` kites.
+ * Identified parameters (the reference's REF_P order, :120-121), as
+ * kite_params fields:
+ *   CL0 CLa_total CD0_total CYb Cm0 Cma Cnb Clb CLq Cmq CYr Cnr Clr CYp Clp
+ *   Cnp CLde CYdr Cmde Cndr Cldr
+ * everything else of a kite's kite_params row is a known constant of that kite.
+ * Log per kite: X (T+1) x 13, U T x 3 (T, dE, dR), sample interval h.
+ *   model      RK4, `substeps` substeps of h / substeps under the held control,
+ *              no wind (the plant's integrator)
+ *   segments   the log is cut into segments of `segment` = L samples; a segment
+ *              starts at the measured X[k0] with zero sensitivity and predicts
+ *              x^_{k0+1} .. x^_{k0+L} (the last one may be shorter).  L = 1: the
+ *              one-step prediction error; L = T: single shooting
+ *   variables  z_j = (p_j - pref_j) / s_j, s_j = |pref_j| (1 where that is 0),
+ *              pref the kite's input row
+ *   cost       c = 1/T sum_k e_k' Q e_k + alpha |z|^2,  e_k = X[k] - x^_k
+ *   normal eq. A = 1/T sum S~' Q S~ + alpha I,  g = 1/T sum S~' Q e - alpha z,
+ *              S~ = (d x^_k / d p) diag(s)
+ *   box        -lb_rel <= z <= ub_rel (+INFINITY: that side is free)
+ * Iteration (per kite, `iters` evaluations, all on the device): evaluate c, A,
+ * g at the trial; accept it when c is finite and not above the accepted cost
+ * (lambda /= 4, floor 1e-12), else reject (lambda *= 8, cap 1e6); active set =
+ * variables on a bound whose gradient points outward; solve
+ * (A + lambda tr(A)/21 I) s = g on the free variables (Cholesky; a pivot <= 0 or
+ * non-finite: s = 0, lambda *= 8); trial = clip(z + s); an accepted evaluation
+ * with |s|_inf < tol ends the kite (KITE_IDENT_CONVERGED).  The result is the
+ * last accepted point: always an evaluated one, its cost never above the first. */
+#define KITE_IDENT_NP        21
+#define KITE_IDENT_CHUNK      8  /* samples per partial sum of the accumulation kernel
+                                    (whole segments: max(1, 8 / L) segments of L)    */
+#define KITE_IDENT_NAN        1  /* log or parameter row non-finite (or not a model), or
+                                    no evaluation was finite: the input row is returned */
+#define KITE_IDENT_CONVERGED  2
+#define KITE_IDENT_AT_BOUND   4  /* some identified parameter ends on its box        */
+typedef struct kite_ident_config {
+    int32_t substeps;     /* RK4 substeps per sample interval, 1..64 (4)             */
+    int32_t segment;      /* L, samples per segment, 1..T (1)                        */
+    int32_t iters;        /* evaluations, 1..64 (12)                                 */
+    int32_t reserved;
+    double h;             /* sample interval [s] (0.02)                              */
+    double Q[13];         /* per-state weight (kite_identification_test.cpp:193)     */
+    double alpha;         /* weight of |z|^2 (0; the reference's fitting_error2: 100) */
+    double lm0;           /* initial lambda (1e-6)                                   */
+    double tol;           /* convergence: |s|_inf of an accepted evaluation (1e-10)  */
+    double lb_rel[21], ub_rel[21];   /* box of z (:127-148)                          */
+} kite_ident_config;
+void kite_ident_default_config(kite_ident_config* cfg);
+/* kite_params field index (0..51) of identified parameter j, -1 outside 0..20. */
+int kite_ident_param_index(int32_t j);
+/* Building block: one sample interval per item.  x13_out (count x 13) and
+ * S = d x+ / d p (count x 13 x 21, unscaled) after `substeps` RK4 substeps of
+ * h / substeps.  params: nparams rows, nparams == 1 (one row for all) or count;
+ * a row that is no model (kite_nmpc_plant_set_params' rule): KITE_EINVAL.     */
+int kite_nmpc_ident_sens(kite_nmpc_ctx* ctx, int32_t count, double h, int32_t substeps,
+                         const kite_params* params, int32_t nparams, const double* x13, const double* u3,
+                         double* x13_out, double* S);
+/* One evaluation at p21 (count x 21 parameter values): A (count x 21 x 21, full,
+ * exactly symmetric), g (count x 21), cost (count) in the scaled variables;
+ * status (count, nullable): KITE_IDENT_NAN where the cost is not finite.
+ * cfg->iters, lm0, tol and the box are not used.                              */
+int kite_nmpc_ident_normal(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                           const kite_params* params, int32_t nparams, const double* p21, const double* X,
+                           const double* U, double* A, double* g, double* cost, int32_t* status);
+/* The identification.  params_out count x 52 (the input row with the 21
+ * replaced), cost2 count x 2 (first and final accepted cost), evals count
+ * (evaluations done), status count (KITE_IDENT_* bits, written on every call);
+ * the last three are nullable.  A row with a non-finite field is contained
+ * (KITE_IDENT_NAN, the other kites are not affected); a finite row that is no
+ * model is KITE_EINVAL.  T < 1, T > 2^20, substeps outside 1..64, segment
+ * outside 1..T, iters outside 1..64, h <= 0 or non-finite, a negative or
+ * non-finite Q / alpha / lm0 / tol, a negative or NaN lb_rel / ub_rel:
+ * KITE_EINVAL, nothing is launched.  count is free of the context's batch.   */
+int kite_nmpc_identify(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                       const kite_params* params, int32_t nparams, const double* X, const double* U,
+                       kite_params* params_out, double* cost2, int32_t* evals, int32_t* status);
+/* Same on device pointers (d_params: nparams x 52 doubles) with a workspace of
+ * kite_nmpc_ident_workspace_doubles doubles: 2 * iters launches on the context
+ * stream, no allocation, no copy, no synchronisation.  The device cannot refuse
+ * a row: one that is no model is KITE_IDENT_NAN.                              */
+int kite_nmpc_identify_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                              const double* d_params, int32_t nparams, const double* d_X, const double* d_U,
+                              double* d_params_out, double* d_cost2, int32_t* d_evals, int32_t* d_status,
+                              double* d_workspace);
+/* Workspace of the device variant in doubles; KITE_EINVAL (negative) for
+ * arguments kite_nmpc_identify refuses.                                       */
+int64_t kite_nmpc_ident_workspace_doubles(const kite_ident_config* cfg, int32_t count, int32_t T);
 
 /* Per-kernel device time [ms] of the last step (cfg.timing = 1):
  * [prologue, rk4_sens, condense, qp, total, qp_main]; qp is the whole QP

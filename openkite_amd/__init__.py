@@ -6,6 +6,8 @@ include/kite_nmpc/kite_nmpc.h); this package is its Python host side.
 from .nmpc import (BatchNMPC, CollocConfig, KiteEKF, KiteNMPF, KiteNmpcError, KiteParams, NmpcConfig, MpcDiagnostic,  # noqa: F401
                    colloc_default_config, default_config, ekf_default_covariances, load_properties, lib, LIB_PATH, DIAG_FIELDS,
                    path_eval, perturb_params, resolve_qp_kernel, PERTURB_FIELDS, PLANT_NAN,
-                   wind_ekf_default_covariances, EKF_NAN, EKF_S_NOT_PD, WIND_MAX_DEFAULT)
+                   wind_ekf_default_covariances, EKF_NAN, EKF_S_NOT_PD, WIND_MAX_DEFAULT,
+                   IdentConfig, IdentResult, ident_default_config, ident_param_index, ident_workspace_doubles,
+                   save_properties, IDENT_FIELDS, IDENT_NP, IDENT_CHUNK, IDENT_NAN, IDENT_CONVERGED, IDENT_AT_BOUND)
 
 __version__ = "0.1.0"

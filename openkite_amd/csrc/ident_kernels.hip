@@ -1,0 +1,420 @@
+// ident_kernels.hip -- batched identification of the 21 aerodynamic
+// coefficients from flight logs on gfx950 (kite_identification_test.cpp as a
+// Gauss-Newton / Levenberg-Marquardt iteration on the device; the formulation
+// is in kite_nmpc.h).
+//
+// k_ident_accum  the hot path.  Per (kite, chunk of whole segments): the
+//   prediction, its forward sensitivities with respect to the 21 through RK4
+//   in variational form -- per stage dK = (df/dx) dX + df/dp_j, the first term
+//   from kite_rhs<Dual> with dX as the tangent seed, the second analytic
+//   (kite_model_dp.hpp) -- and the partial sums of S~'QS~ (upper triangle, 231
+//   values), S~'Qe and e'Qe.
+//   Lane layout: lanes are directions.  A 64-lane block holds 3 items of 21
+//   lanes (lane 63 idles); lane j of an item carries column j of S~, already
+//   scaled by s_j.  The 13 x 21 sensitivity of a sample is exchanged through
+//   LDS and lane j accumulates column j of the products on VALU (13 x 21
+//   multiply-adds per lane and sample).  An item's model constants, formed
+//   from its kite_params row and the trial parameters, sit in LDS too.
+//   Reduction: no atomics.  An item stores its partials to the workspace slab
+//   [kite][chunk][256]; k_ident_solve sums them in ascending chunk order, so a
+//   kite's result does not depend on the batch around it.
+// k_ident_solve  one block per kite: that sum, the accept / reject decision,
+//   the active set, the 21 x 21 Cholesky (lane i owns row i, in LDS), the
+//   clipped trial, status and lambda.  With `normal` it stops after the sum and
+//   writes A, g and the cost (kite_nmpc_ident_normal).
+// k_ident_sens   one sample interval per item: x+ and d x+ / d p (unscaled).
+//
+// Barriers: the items of a block share every barrier.  No lane returns or
+// leaves a loop early, all trip counts are kernel arguments; an out-of-range
+// or finished item is predicated, loads zeros and stores nothing.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "ident_kernels.hpp"
+#include "kite_model.hpp"
+#include "kite_model_dp.hpp"
+#include "kite_nmpc/kite_nmpc.h"
+
+namespace kite {
+
+constexpr int ID_T = 64;              // threads per block
+constexpr int ID_ITEMS = 3;           // items of 21 lanes per block
+constexpr int ID_LD = NP + 1;         // LDS row stride of a 13 x 21 sensitivity
+
+// the sample interval under the held control for direction j: x (value and
+// tangent column j, scaled by sc) advanced by `substeps` RK4 substeps of hs.
+// The value part repeats plant_lane's (plant_kernels.hip) stage arithmetic.
+__device__ __forceinline__ void ident_interval(const ModelConst& P, Dual* x, const double* u, double hs, int substeps,
+                                               int j, double sc) {
+    Dual ud[NKU];
+#pragma unroll
+    for (int i = 0; i < NKU; ++i) ud[i] = mk(u[i], 0.0);
+#pragma unroll 1
+    for (int m = 0; m < substeps; ++m) {
+        Dual xs[NK], acc[NK], kv[NK];
+#pragma unroll
+        for (int i = 0; i < NK; ++i) { xs[i] = x[i]; acc[i] = x[i]; }
+#pragma unroll 1
+        for (int st = 0; st < 4; ++st) {
+            // the model constants are read from LDS in every stage: hoisted out of
+            // the loops they would hold 94 registers next to the RK4 state
+            asm volatile("" ::: "memory");
+            kite_rhs<Dual>(P, xs, ud, kv);
+            double xv[6], fp[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) xv[i] = xs[i].v;
+            kite_rhs_dp(P, xv, u, j, sc, fp);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) kv[i].t += fp[i];
+            const double wa = (st == 0 || st == 3) ? hs / 6.0 : hs / 3.0;
+            const double wn = (st < 2) ? 0.5 * hs : hs;
+#pragma unroll
+            for (int i = 0; i < NK; ++i) {
+                acc[i].v += wa * kv[i].v;
+                acc[i].t += wa * kv[i].t;
+                xs[i].v = x[i].v + wn * kv[i].v;
+                xs[i].t = x[i].t + wn * kv[i].t;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NK; ++i) x[i] = acc[i];
+    }
+}
+
+// lane -> (item of the block, direction); lane 63 belongs to no item
+struct IdLane { int it, j; bool on; };
+__device__ __forceinline__ IdLane id_lane() {
+    const int t = threadIdx.x;
+    const int it = t / NP;
+    return IdLane{it, t - it * NP, it < ID_ITEMS};
+}
+
+// the item's model constants into LDS (lane 0 of the item), and its scale s_j
+__device__ __forceinline__ double id_setup(ModelConst* sP, const IdLane& l, bool valid, const double* row,
+                                           const double* p21) {
+    double sc = 1.0;
+    if (valid) {
+        const double pr = row[ident_field(l.j)];
+        sc = pr != 0.0 ? fabs(pr) : 1.0;
+        if (l.j == 0) sP[l.it] = ident_model_const(row, p21);
+    }
+    return sc;
+}
+
+__global__ __launch_bounds__(ID_T) void k_ident_accum(IdentConst C, const double* __restrict__ rows,
+                                                      const double* __restrict__ p21, int p_stride,
+                                                      const double* __restrict__ state,
+                                                      const double* __restrict__ X, const double* __restrict__ U,
+                                                      double* __restrict__ slab) {
+    __shared__ ModelConst sP[ID_ITEMS + 1];
+    __shared__ double sS[(ID_ITEMS + 1) * NK * ID_LD];
+    const IdLane l = id_lane();
+    const long long item = (long long)blockIdx.x * ID_ITEMS + l.it;
+    const int kite = (int)(item / C.nchunks), chunk = (int)(item - (long long)kite * C.nchunks);
+    bool valid = l.on && kite < C.count;
+    // a kite that is finished (converged, or its row is no model) does no further work
+    if (valid && state) valid = ((int)state[(size_t)kite * ID_STATE + ID_S_FLAGS] & (ID_F_DONE | ID_F_DEAD)) == 0;
+    const double* row = rows + (size_t)(C.nparams == 1 ? 0 : (valid ? kite : 0)) * 52;
+    const double sc = id_setup(sP, l, valid, row, p21 ? p21 + (size_t)(valid ? kite : 0) * p_stride : nullptr);
+    __syncthreads();
+    const ModelConst& P = sP[l.it];
+    double* sm = sS + l.it * NK * ID_LD;
+    const double* Xk = X + (size_t)(valid ? kite : 0) * (C.T + 1) * NK;
+    const double* Uk = U + (size_t)(valid ? kite : 0) * C.T * NKU;
+
+    double aA[NP], ag = 0.0, ac = 0.0;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) aA[i] = 0.0;
+
+    if (__any(valid)) {                      // uniform over the block (one wavefront)
+#pragma unroll 1
+        for (int sg = 0; sg < C.spc; ++sg) {
+            const long long k0 = ((long long)chunk * C.spc + sg) * C.L;
+            const bool sv = valid && k0 < C.T;
+            Dual x[NK];
+#pragma unroll
+            for (int i = 0; i < NK; ++i) x[i] = mk(sv ? Xk[(size_t)k0 * NK + i] : 0.0, 0.0);
+#pragma unroll 1
+            for (int a = 0; a < C.L; ++a) {
+                const long long k = k0 + a;
+                const bool on = sv && k < C.T;
+                double u[NKU];
+#pragma unroll
+                for (int i = 0; i < NKU; ++i) u[i] = on ? Uk[(size_t)k * NKU + i] : 0.0;
+                ident_interval(P, x, u, C.hs, C.substeps, l.j, sc);
+                // column j of S~ and (lane 0) the residual e into LDS: row r holds
+                // S~[r][0..20] and e_r
+#pragma unroll
+                for (int r = 0; r < NK; ++r) sm[r * ID_LD + l.j] = x[r].t;
+                if (l.j == 0)
+#pragma unroll
+                    for (int r = 0; r < NK; ++r) sm[r * ID_LD + NP] = on ? Xk[(size_t)(k + 1) * NK + r] - x[r].v : 0.0;
+                __syncthreads();
+                if (on) {
+#pragma unroll 1
+                    for (int r = 0; r < NK; ++r) {
+                        const double* sr = sm + r * ID_LD;
+                        const double e = sr[NP], q = C.Q[r];
+                        const double qe = q * e;
+                        const double t = q * sr[l.j];
+                        ac = fma(qe, e, ac);
+                        ag = fma(sr[l.j], qe, ag);
+#pragma unroll
+                        for (int i = 0; i < NP; ++i) aA[i] = fma(sr[i], t, aA[i]);
+                    }
+                }
+                __syncthreads();             // sm is rewritten by the next sample
+            }
+        }
+    }
+    if (valid) {
+        double* out = slab + ((size_t)kite * C.nchunks + chunk) * ID_SLAB;
+        const int base = l.j * (l.j + 1) / 2;            // A[i][j], i <= j, packed by columns
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+            if (i <= l.j) out[base + i] = aA[i];
+        out[ID_SLAB_G + l.j] = ag;
+        if (l.j == 0) out[ID_SLAB_C] = ac;
+    }
+}
+
+__device__ __forceinline__ int id_packed(int i, int j) {      // index of A[i][j] in the packed upper triangle
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    return hi * (hi + 1) / 2 + lo;
+}
+
+__global__ __launch_bounds__(ID_T) void k_ident_solve(IdentConst C, int first, int normal,
+                                                      const double* __restrict__ rows,
+                                                      const double* __restrict__ p21,
+                                                      const double* __restrict__ slab, double* __restrict__ state,
+                                                      double* __restrict__ Aout, double* __restrict__ gout,
+                                                      double* __restrict__ cout, double* __restrict__ params_out,
+                                                      double* __restrict__ cost2, int32_t* __restrict__ evals,
+                                                      int32_t* __restrict__ status) {
+    __shared__ double sR[ID_SLAB];            // the chunk sums
+    __shared__ double sAA[ID_NA];             // A of the accepted point (packed, without alpha I)
+    __shared__ double sM[NP * ID_LD];         // that A + damping, then its Cholesky factor (lower)
+    __shared__ double sz[NP], sg[NP], sy[NP], ss[NP];
+    __shared__ int sok;
+    const int t = threadIdx.x, kite = blockIdx.x;
+    const double* row = rows + (size_t)(C.nparams == 1 ? 0 : kite) * 52;
+    double* st = state ? state + (size_t)kite * ID_STATE : nullptr;
+
+    // the kite's row is a model (every lane looks at a share of it; uniform)
+    bool rok = true;
+    if (t < 52) rok = isfinite(row[t]);
+    rok = !__any(!rok) && (row[10] > 0.0) && (row[11] * row[13] - row[14] * row[14] != 0.0) && (row[12] != 0.0);
+
+    int flags = 0;
+    if (!normal) flags = first ? (rok ? 0 : ID_F_DEAD) : (int)st[ID_S_FLAGS];
+    const bool live = normal || (flags & (ID_F_DONE | ID_F_DEAD)) == 0;    // uniform over the block
+
+    // 1. the partial sums in ascending chunk order
+    for (int e = t; e < ID_SLAB; e += ID_T) {
+        double s = 0.0;
+        if (live && e <= ID_SLAB_C)
+#pragma unroll 1
+            for (int c = 0; c < C.nchunks; ++c) s += slab[((size_t)kite * C.nchunks + c) * ID_SLAB + e];
+        sR[e] = s;
+    }
+    const double pr = t < NP ? row[ident_field(t)] : 0.0;
+    const double sc = pr != 0.0 ? fabs(pr) : 1.0;
+    double z = 0.0;                            // the point of this evaluation
+    if (t < NP) {
+        if (normal) z = (p21[(size_t)kite * NP + t] - pr) / sc;
+        else if (!first) z = st[ID_S_ZT + t];
+        sz[t] = z;
+    }
+    __syncthreads();
+    const double T = (double)C.T;
+    double c = sR[ID_SLAB_C] / T;
+    {
+        double zz = 0.0;
+#pragma unroll 1
+        for (int i = 0; i < NP; ++i) zz = fma(sz[i], sz[i], zz);
+        c += C.alpha * zz;
+    }
+    const double g = t < NP ? sR[ID_SLAB_G + t] / T - C.alpha * z : 0.0;
+
+    if (normal) {                              // uniform
+        if (t < NP) {
+#pragma unroll 1
+            for (int i = 0; i < NP; ++i)
+                Aout[((size_t)kite * NP + i) * NP + t] = sR[id_packed(i, t)] / T + (i == t ? C.alpha : 0.0);
+            gout[(size_t)kite * NP + t] = g;
+        }
+        if (t == 0) {
+            cout[kite] = c;
+            if (status) status[kite] = (isfinite(c) && rok) ? 0 : KITE_IDENT_NAN;
+        }
+        return;                                // the whole block
+    }
+
+    double lam = first ? C.lm0 : st[ID_S_LAM];
+    double c_acc = first ? 0.0 : st[ID_S_CACC];
+    double c0 = first ? 0.0 : st[ID_S_C0];
+    int nev = first ? 0 : (int)st[ID_S_EVALS];
+    double z_acc = (t < NP && !first) ? st[ID_S_ZA + t] : 0.0;
+    double g_acc = (t < NP && !first) ? st[ID_S_GA + t] : 0.0;
+    double z_trial = z;
+    const double lo = t < NP ? -C.lb_rel[t] : 0.0, hi = t < NP ? C.ub_rel[t] : 0.0;
+
+    if (live) {                                // uniform: the barriers below are shared
+        ++nev;
+        // 2. accept or reject
+        const bool accept = isfinite(c) && (!(flags & ID_F_ACC) || c <= c_acc);
+        if (accept) {
+            if (!(flags & ID_F_ACC)) c0 = c;
+            flags |= ID_F_ACC;
+            c_acc = c;
+            z_acc = z;
+            g_acc = g;
+            for (int e = t; e < ID_NA; e += ID_T) { sAA[e] = sR[e] / T; st[ID_S_AA + e] = sAA[e]; }
+            lam = fmax(lam * 0.25, 1e-12);
+        } else {
+            if (flags & ID_F_ACC)
+                for (int e = t; e < ID_NA; e += ID_T) sAA[e] = st[ID_S_AA + e];
+            lam = fmin(8.0 * lam, 1e6);
+        }
+        __syncthreads();
+        if (flags & ID_F_ACC) {                // uniform
+            // 3. active set, 4. damped normal equations on the free variables
+            const bool act = t < NP && ((z_acc <= lo && g_acc < 0.0) || (z_acc >= hi && g_acc > 0.0));
+            if (t < NP) { sy[t] = act ? 1.0 : 0.0; sg[t] = act ? 0.0 : g_acc; }
+            __syncthreads();
+            double tr = 0.0;
+#pragma unroll 1
+            for (int i = 0; i < NP; ++i) tr += sAA[id_packed(i, i)] + C.alpha;
+            const double damp = lam * tr / (double)NP;
+            if (t < NP)
+#pragma unroll 1
+                for (int i = 0; i < NP; ++i) {
+                    double v = sAA[id_packed(t, i)] + (i == t ? C.alpha + damp : 0.0);
+                    if (act || sy[i] != 0.0) v = i == t ? 1.0 : 0.0;
+                    sM[t * ID_LD + i] = v;
+                }
+            if (t == 0) sok = 1;
+            __syncthreads();
+            // Cholesky, right-looking; lane i owns row i
+#pragma unroll 1
+            for (int k = 0; k < NP; ++k) {
+                const double d = sM[k * ID_LD + k];
+                const bool pd = d > 0.0 && isfinite(d);
+                const double dd = pd ? sqrt(d) : 1.0;
+                const double lik = (t < NP && t > k) ? sM[t * ID_LD + k] / dd : 0.0;
+                __syncthreads();
+                if (t == k) { sM[k * ID_LD + k] = dd; if (!pd) sok = 0; }
+                if (t < NP && t > k) sM[t * ID_LD + k] = lik;
+                __syncthreads();
+                if (t < NP && t > k)
+#pragma unroll 1
+                    for (int i = k + 1; i <= t; ++i) sM[t * ID_LD + i] -= lik * sM[i * ID_LD + k];
+                __syncthreads();
+            }
+            if (t == 0) {                      // L y = g, L' s = y
+#pragma unroll 1
+                for (int i = 0; i < NP; ++i) {
+                    double v = sg[i];
+#pragma unroll 1
+                    for (int k = 0; k < i; ++k) v -= sM[i * ID_LD + k] * sy[k];
+                    sy[i] = v / sM[i * ID_LD + i];
+                }
+#pragma unroll 1
+                for (int i = NP - 1; i >= 0; --i) {
+                    double v = sy[i];
+#pragma unroll 1
+                    for (int k = i + 1; k < NP; ++k) v -= sM[k * ID_LD + i] * ss[k];
+                    ss[i] = v / sM[i * ID_LD + i];
+                }
+            }
+            __syncthreads();
+            const bool ok = sok != 0;
+            double snorm = 0.0;
+#pragma unroll 1
+            for (int i = 0; i < NP; ++i) snorm = fmax(snorm, ok ? fabs(ss[i]) : 0.0);
+            if (!ok) lam = fmin(8.0 * lam, 1e6);
+            // 5. the clipped trial, 6. convergence
+            if (t < NP) z_trial = fmin(fmax(z_acc + (ok ? ss[t] : 0.0), lo), hi);
+            if (accept && snorm < C.tol) flags |= ID_F_DONE;
+        }
+    }
+
+    // state, trial and outputs (every call: the last one stands)
+    const bool have = (flags & ID_F_ACC) && !(flags & ID_F_DEAD);
+    if (t < NP) {
+        st[ID_S_ZT + t] = z_trial;
+        st[ID_S_PT + t] = pr + sc * z_trial;
+        st[ID_S_ZA + t] = z_acc;
+        st[ID_S_GA + t] = g_acc;
+    }
+    if (t == 0) {
+        st[ID_S_LAM] = lam; st[ID_S_CACC] = c_acc; st[ID_S_C0] = c0;
+        st[ID_S_FLAGS] = (double)flags; st[ID_S_EVALS] = (double)nev;
+    }
+    if (t < 52) params_out[(size_t)kite * 52 + t] = row[t];
+    __syncthreads();                           // the row first, then the 21 over it
+    const bool atb = t < NP && have && (z_acc <= lo || z_acc >= hi);
+    const bool any_atb = __any(atb);
+    if (t < NP && have) params_out[(size_t)kite * 52 + ident_field(t)] = pr + sc * z_acc;
+    if (t == 0) {
+        if (cost2) { cost2[2 * (size_t)kite] = have ? c0 : NAN; cost2[2 * (size_t)kite + 1] = have ? c_acc : NAN; }
+        if (evals) evals[kite] = nev;
+        if (status)
+            status[kite] = have ? (((flags & ID_F_DONE) ? KITE_IDENT_CONVERGED : 0) | (any_atb ? KITE_IDENT_AT_BOUND : 0))
+                                : KITE_IDENT_NAN;
+    }
+}
+
+__global__ __launch_bounds__(ID_T) void k_ident_sens(int count, int nparams, double hs, int substeps,
+                                                     const double* __restrict__ rows,
+                                                     const double* __restrict__ x13, const double* __restrict__ u3,
+                                                     double* __restrict__ xo, double* __restrict__ S) {
+    __shared__ ModelConst sP[ID_ITEMS + 1];
+    const IdLane l = id_lane();
+    const long long item = (long long)blockIdx.x * ID_ITEMS + l.it;
+    const bool valid = l.on && item < count;
+    const size_t b = valid ? (size_t)item : 0;
+    const double* row = rows + (nparams == 1 ? 0 : b) * 52;
+    id_setup(sP, l, valid, row, nullptr);
+    __syncthreads();
+    Dual x[NK];
+    double u[NKU];
+#pragma unroll
+    for (int i = 0; i < NK; ++i) x[i] = mk(valid ? x13[b * NK + i] : 0.0, 0.0);
+#pragma unroll
+    for (int i = 0; i < NKU; ++i) u[i] = valid ? u3[b * NKU + i] : 0.0;
+    ident_interval(sP[l.it], x, u, hs, substeps, l.j, 1.0);
+    if (valid) {
+#pragma unroll
+        for (int r = 0; r < NK; ++r) S[(b * NK + r) * NP + l.j] = x[r].t;
+        if (l.j == 0)
+#pragma unroll
+            for (int r = 0; r < NK; ++r) xo[b * NK + r] = x[r].v;
+    }
+}
+
+hipError_t launch_ident_accum(const IdentConst& C, const double* rows, const double* p21, int p_stride,
+                              const double* state, const double* X, const double* U, double* slab, hipStream_t s) {
+    const long long items = (long long)C.count * C.nchunks;
+    hipLaunchKernelGGL(k_ident_accum, dim3((unsigned)((items + ID_ITEMS - 1) / ID_ITEMS)), dim3(ID_T), 0, s, C, rows,
+                       p21, p_stride, state, X, U, slab);
+    return hipGetLastError();
+}
+
+hipError_t launch_ident_solve(const IdentConst& C, int first, int normal, const double* rows, const double* p21,
+                              const double* slab, double* state, double* A, double* g, double* cost,
+                              double* params_out, double* cost2, int32_t* evals, int32_t* status, hipStream_t s) {
+    hipLaunchKernelGGL(k_ident_solve, dim3(C.count), dim3(ID_T), 0, s, C, first, normal, rows, p21, slab, state, A, g,
+                       cost, params_out, cost2, evals, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_ident_sens(int count, int nparams, double hs, int substeps, const double* rows, const double* x13,
+                             const double* u3, double* xo, double* S, hipStream_t s) {
+    hipLaunchKernelGGL(k_ident_sens, dim3((count + ID_ITEMS - 1) / ID_ITEMS), dim3(ID_T), 0, s, count, nparams, hs,
+                       substeps, rows, x13, u3, xo, S);
+    return hipGetLastError();
+}
+
+}  // namespace kite

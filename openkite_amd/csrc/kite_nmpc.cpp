@@ -19,6 +19,8 @@
 #include <vector>
 
 #include "kite_nmpc/kite_nmpc.h"
+#include "ident_kernels.hpp"
+#include "kite_model_dp.hpp"
 #include "rti_kernels.hpp"
 
 using kite::ModelConst;
@@ -1255,6 +1257,178 @@ int kite_nmpc_set_wind_device(kite_nmpc_ctx* ctx, const double* d_wind, int32_t 
         ++ctx->graph_gen;
     }
     return KITE_OK;
+}
+
+// ---- aerodynamic parameter identification (ident_kernels.hip) ----------------
+void kite_ident_default_config(kite_ident_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->substeps = 4; c->segment = 1; c->iters = 12;
+    c->h = 0.02;
+    // kite_identification_test.cpp:193
+    const double Q[13] = {1e3, 1e2, 1e2, 1e2, 1e2, 1e2, 1e1, 1e1, 1e2, 1e2, 1e2, 1e2, 1e2};
+    for (int i = 0; i < 13; ++i) c->Q[i] = Q[i];
+    c->alpha = 0.0;       // the live cost has no regulariser (:208 is commented out; fitting_error2 uses 100)
+    c->lm0 = 1e-6; c->tol = 1e-10;
+    // kite_identification_test.cpp:127-148, relative to |REF_P|
+    const double lb[21] = {0.1, 0.05, 0.1, 0.5, 0.5, 0.1, 0.5, 0.5, 0.2, 0.3, 0.3,
+                           0.5, 0.5, 0.5, 0.5, 0.3, 0.5, 0.5, 0.5, 0.5, 0.5};
+    const double ub[21] = {0.1, 0.1, 0.25, 0.5, 0.5, 0.3, 0.5, 0.5, 0.2, 0.3, 0.3,
+                           0.5, 0.5, 0.5, 0.5, 1.0, 0.5, 0.5, 0.5, 0.5, 0.5};
+    for (int j = 0; j < 21; ++j) { c->lb_rel[j] = lb[j]; c->ub_rel[j] = ub[j]; }
+}
+
+int kite_ident_param_index(int32_t j) { return (j >= 0 && j < KITE_IDENT_NP) ? kite::ident_field(j) : -1; }
+
+extern "C++" {
+namespace {
+// the evaluation's constants from a validated config; KITE_EINVAL otherwise
+int make_ident_const(const kite_ident_config* cfg, int32_t count, int32_t T, int32_t nparams, kite::IdentConst* out) {
+    if (!cfg || count < 1 || (nparams != 1 && nparams != count)) return KITE_EINVAL;
+    const kite_ident_config& c = *cfg;
+    if (T < 1 || T > (1 << 20) || c.substeps < 1 || c.substeps > 64 || c.segment < 1 || c.segment > T) return KITE_EINVAL;
+    if (c.iters < 1 || c.iters > 64 || !std::isfinite(c.h) || !(c.h > 0.0)) return KITE_EINVAL;
+    auto nonneg = [](double v) { return std::isfinite(v) && v >= 0.0; };
+    for (int i = 0; i < 13; ++i) if (!nonneg(c.Q[i])) return KITE_EINVAL;
+    if (!nonneg(c.alpha) || !nonneg(c.lm0) || !nonneg(c.tol)) return KITE_EINVAL;
+    for (int j = 0; j < KITE_IDENT_NP; ++j)                   // +INFINITY: that side is free
+        if (!(c.lb_rel[j] >= 0.0) || !(c.ub_rel[j] >= 0.0)) return KITE_EINVAL;
+    kite::IdentConst k;
+    std::memset(&k, 0, sizeof(k));
+    k.count = count; k.nparams = nparams; k.T = T; k.L = c.segment; k.substeps = c.substeps;
+    k.spc = std::max(1, KITE_IDENT_CHUNK / c.segment);
+    const int64_t nseg = ((int64_t)T + c.segment - 1) / c.segment;
+    k.nchunks = (int)((nseg + k.spc - 1) / k.spc);
+    if ((int64_t)count * k.nchunks > ((int64_t)1 << 31) - 64) return KITE_EINVAL;    // the grid
+    k.hs = c.h / c.substeps;
+    for (int i = 0; i < 13; ++i) k.Q[i] = c.Q[i];
+    k.alpha = c.alpha; k.lm0 = c.lm0; k.tol = c.tol;
+    for (int j = 0; j < KITE_IDENT_NP; ++j) { k.lb_rel[j] = c.lb_rel[j]; k.ub_rel[j] = c.ub_rel[j]; }
+    *out = k;
+    return KITE_OK;
+}
+
+// host-side check of the rows: a finite row must be a model; with `contain` a
+// row with a non-finite field passes (the kernels flag that kite)
+int ident_rows_ok(const kite_params* params, int32_t nparams, bool contain) {
+    if (!params) return KITE_EINVAL;
+    for (int32_t b = 0; b < nparams; ++b) {
+        const double* f = reinterpret_cast<const double*>(&params[b]);
+        bool fin = true;
+        for (int i = 0; i < 52; ++i) fin = fin && std::isfinite(f[i]);
+        if (!fin && contain) continue;
+        ModelConst m;
+        if (!plant_params_ok(params[b], &m)) return KITE_EINVAL;
+    }
+    return KITE_OK;
+}
+
+int ident_run_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, const kite::IdentConst& K, const double* d_rows,
+                     const double* d_X, const double* d_U, double* d_out, double* d_cost2, int32_t* d_evals,
+                     int32_t* d_status, double* ws) {
+    double* state = ws;
+    double* slab = ws + (size_t)K.count * kite::ID_STATE;
+    hipStream_t s = ctx->stream;
+    for (int it = 0; it < cfg->iters; ++it) {
+        const int first = it == 0;
+        HIP_TRY(kite::launch_ident_accum(K, d_rows, first ? nullptr : state + kite::ID_S_PT, kite::ID_STATE,
+                                         first ? nullptr : state, d_X, d_U, slab, s));
+        HIP_TRY(kite::launch_ident_solve(K, first, 0, d_rows, nullptr, slab, state, nullptr, nullptr, nullptr, d_out,
+                                         d_cost2, d_evals, d_status, s));
+    }
+    return KITE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int64_t kite_nmpc_ident_workspace_doubles(const kite_ident_config* cfg, int32_t count, int32_t T) {
+    kite::IdentConst K;
+    const int rc = make_ident_const(cfg, count, T, 1, &K);
+    if (rc) return rc;
+    return (int64_t)count * kite::ID_STATE + (int64_t)count * K.nchunks * kite::ID_SLAB;
+}
+
+int kite_nmpc_ident_sens(kite_nmpc_ctx* ctx, int32_t count, double h, int32_t substeps, const kite_params* params,
+                         int32_t nparams, const double* x13, const double* u3, double* x13_out, double* S) {
+    if (!ctx || count < 1 || !x13 || !u3 || !x13_out || !S || (nparams != 1 && nparams != count)) return KITE_EINVAL;
+    if (!std::isfinite(h) || !(h > 0.0) || substeps < 1 || substeps > 64) return KITE_EINVAL;
+    const int rc = ident_rows_ok(params, nparams, false);
+    if (rc) return rc;
+    const size_t c = count;
+    return run_items(ctx, {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {x13, c * 13}, {u3, c * 3}},
+                     {{x13_out, c * 13}, {S, c * 13 * KITE_IDENT_NP}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         return kite::launch_ident_sens(count, nparams, h / substeps, substeps, i[0], i[1], i[2], o[0],
+                                                        o[1], s);
+                     });
+}
+
+int kite_nmpc_ident_normal(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                           const kite_params* params, int32_t nparams, const double* p21, const double* X,
+                           const double* U, double* A, double* g, double* cost, int32_t* status) {
+    if (!ctx || !p21 || !X || !U || !A || !g || !cost) return KITE_EINVAL;
+    kite::IdentConst K;
+    int rc = make_ident_const(cfg, count, T, nparams, &K);
+    if (rc) return rc;
+    rc = ident_rows_ok(params, nparams, true);
+    if (rc) return rc;
+    const size_t c = count, NPq = KITE_IDENT_NP;
+    return run_items(ctx,
+                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {p21, c * NPq},
+                      {X, c * (T + 1) * 13}, {U, c * T * 3}},
+                     {{A, c * NPq * NPq}, {g, c * NPq}, {cost, c}, {nullptr, (c + 1) / 2},
+                      {nullptr, c * K.nchunks * kite::ID_SLAB}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         int32_t* dst = reinterpret_cast<int32_t*>(o[3]);
+                         hipError_t e = kite::launch_ident_accum(K, i[0], i[1], KITE_IDENT_NP, nullptr, i[2], i[3], o[4], s);
+                         if (e != hipSuccess) return e;
+                         e = kite::launch_ident_solve(K, 0, 1, i[0], i[1], o[4], nullptr, o[0], o[1], o[2], nullptr,
+                                                      nullptr, nullptr, dst, s);
+                         if (e != hipSuccess || !status) return e;
+                         return hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+                     });
+}
+
+int kite_nmpc_identify_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                              const double* d_params, int32_t nparams, const double* d_X, const double* d_U,
+                              double* d_params_out, double* d_cost2, int32_t* d_evals, int32_t* d_status,
+                              double* d_workspace) {
+    if (!ctx || !d_params || !d_X || !d_U || !d_params_out || !d_workspace) return KITE_EINVAL;
+    kite::IdentConst K;
+    const int rc = make_ident_const(cfg, count, T, nparams, &K);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return ident_run_device(ctx, cfg, K, d_params, d_X, d_U, d_params_out, d_cost2, d_evals, d_status, d_workspace);
+}
+
+int kite_nmpc_identify(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                       const kite_params* params, int32_t nparams, const double* X, const double* U,
+                       kite_params* params_out, double* cost2, int32_t* evals, int32_t* status) {
+    if (!ctx || !X || !U || !params_out) return KITE_EINVAL;
+    kite::IdentConst K;
+    int rc = make_ident_const(cfg, count, T, nparams, &K);
+    if (rc) return rc;
+    rc = ident_rows_ok(params, nparams, true);
+    if (rc) return rc;
+    const size_t c = count;
+    const size_t ws = (size_t)kite_nmpc_ident_workspace_doubles(cfg, count, T);
+    // int32 outputs (evals, status) share one scratch block of c doubles
+    return run_items(ctx,
+                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {X, c * (T + 1) * 13},
+                      {U, c * T * 3}},
+                     {{reinterpret_cast<double*>(params_out), c * 52}, {cost2, 2 * c}, {nullptr, c}, {nullptr, ws}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         int32_t* dev = reinterpret_cast<int32_t*>(o[2]);
+                         int32_t* dst = dev + c;
+                         if (ident_run_device(ctx, cfg, K, i[0], i[1], i[2], o[0], o[1], dev, dst, o[3]) != KITE_OK)
+                             return hipErrorLaunchFailure;
+                         if (evals) {
+                             hipError_t e = hipMemcpyAsync(evals, dev, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+                             if (e != hipSuccess) return e;
+                         }
+                         if (status) return hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+                         return hipSuccess;
+                     });
 }
 
 int kite_nmpc_rk4_sens(kite_nmpc_ctx* ctx, int32_t count, const double* x15, const double* u4, double tf,

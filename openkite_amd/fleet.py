@@ -87,6 +87,64 @@ class GpuPlant:
                                    status.data_ptr())
 
 
+class FlightRecorder:
+    """Flight log of a fleet on the device for the parameter identification
+    (``BatchNMPC.identify_device``): X (B, T+1, 13) the kite state handed to the
+    controller at the start of each control period, U (B, T, 3) the control
+    (T, dE, dR) applied over it.  ``FleetLoop(recorder=...)`` fills it, one
+    period per step, and it stops when full (``full``)."""
+
+    def __init__(self, B: int, T: int, device=None):
+        f64 = dict(dtype=torch.float64, device=device)
+        self.B, self.T = int(B), int(T)
+        self.X = torch.zeros((self.B, self.T + 1, 13), **f64)
+        self.U = torch.zeros((self.B, self.T, 3), **f64)
+        self.nx = 0            # states recorded
+        self.nu = 0            # controls recorded
+
+    @property
+    def full(self) -> bool:
+        return self.nx == self.T + 1 and self.nu == self.T
+
+    def reset(self):
+        self.nx = self.nu = 0
+
+    def record_state(self, x0: torch.Tensor) -> None:
+        if self.nx <= self.T:
+            self.X[:, self.nx, :].copy_(x0[:, :13])
+            self.nx += 1
+
+    def record_control(self, u0: torch.Tensor) -> None:
+        if self.nu < self.T:
+            self.U[:, self.nu, :].copy_(u0[:, :3])
+            self.nu += 1
+
+    def identify(self, ctx, config, params=None):
+        """Identify every kite's 21 aerodynamic coefficients from the log
+        (asynchronous on the context stream, as the loop's other calls).
+        config: an ``IdentConfig``; for a loop flown against
+        ``GpuPlant(h, steps, substeps)`` with control period dt = h * steps the
+        model that repeats the plant's arithmetic is h = dt, substeps = steps *
+        substeps.  params: the rows the fit starts from (52 values or (B, 52));
+        None: the context's own.  Returns device tensors
+        (params (B, 52), cost2 (B, 2), evals (B,), status (B,))."""
+        from . import nmpc
+        if not self.full:
+            raise ValueError(f"the log holds {self.nx} of {self.T + 1} states")
+        dev = self.X.device
+        rows = torch.from_numpy(ctx._ident_rows(params, self.B).copy()).to(dev)
+        out = torch.zeros((self.B, 52), dtype=torch.float64, device=dev)
+        cost2 = torch.zeros((self.B, 2), dtype=torch.float64, device=dev)
+        evals = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        status = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        ws = torch.empty((nmpc.ident_workspace_doubles(config, self.B, self.T),), dtype=torch.float64, device=dev)
+        ctx.identify_device(config, self.B, self.T, rows.data_ptr(), rows.shape[0], self.X.data_ptr(),
+                            self.U.data_ptr(), out.data_ptr(), cost2.data_ptr(), evals.data_ptr(), status.data_ptr(),
+                            ws.data_ptr())
+        self._keep = (rows, ws)      # alive until the stream has run the launches
+        return out, cost2, evals, status
+
+
 class MeasurementNoise:
     """Seeded Gaussian disturbance of the measured kite state (bench.py
     --meas-noise): per step and kite, body velocity += 0.05 S, body rates +=
@@ -119,7 +177,7 @@ class FleetLoop:
 
     def __init__(self, stepper, x0: torch.Tensor, N: int, dt: float, ekf: bool = False, ekf_substeps: int = 5,
                  covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None,
-                 plant=None, wind_ekf: bool = False, wind_max: float = 20.0):
+                 plant=None, wind_ekf: bool = False, wind_max: float = 20.0, recorder=None):
         if ekf and wind_ekf:
             raise ValueError("ekf and wind_ekf are two estimators: choose one")
         B = x0.shape[0]
@@ -167,6 +225,9 @@ class FleetLoop:
             self.ekf_status = torch.zeros((B,), dtype=torch.int32, device=dev)
             self.wind_ekf_fresh = True
         self.gathered = None
+        # a ``FlightRecorder``: the state handed to the controller and the control
+        # applied, one period per step, until it is full
+        self.recorder = recorder
         # a plant of its own (``GpuPlant``, or any object with h, steps and
         # advance): the loop carries the true kite state xp and the time t
         self.plant = plant
@@ -226,7 +287,11 @@ class FleetLoop:
                 self.stepper.ekf(h, self.xe, self.u3, self.P, self.z if j == self.ekf_substeps - 1 else None,
                                  self.W, self.V)
             self.x0[:, :13].copy_(self.xe)
+        if self.recorder is not None:
+            self.recorder.record_state(self.x0)
         self.stepper.rti(self.x0, self.u0, self.traj, self.diag, self.status)
+        if self.recorder is not None:
+            self.recorder.record_control(self.u0)
         if self.pub is not None:
             self.gathered = self.pub.publish(self.u0, self.diag)
         if self.plant is None:

@@ -26,6 +26,12 @@ ST_RESTART = 64
 PLANT_NAN = 1                      # KITE_PLANT_NAN (plant status word)
 EKF_NAN, EKF_S_NOT_PD = 1, 2       # KITE_EKF_* (status word of the wind-estimating EKF)
 WIND_MAX_DEFAULT = 20.0            # set_wind_device: clamp of an estimated wind component, m/s
+IDENT_NAN, IDENT_CONVERGED, IDENT_AT_BOUND = 1, 2, 4   # KITE_IDENT_* (status word of the identification)
+IDENT_NP = 21                      # KITE_IDENT_NP
+IDENT_CHUNK = 8                    # KITE_IDENT_CHUNK: samples per partial sum of k_ident_accum
+# the identified parameters in the reference's REF_P order (kite_identification_test.cpp:120-121)
+IDENT_FIELDS = ["CL0", "CLa_total", "CD0_total", "CYb", "Cm0", "Cma", "Cnb", "Clb", "CLq", "Cmq",
+                "CYr", "Cnr", "Clr", "CYp", "Clp", "Cnp", "CLde", "CYdr", "Cmde", "Cndr", "Cldr"]
 
 _PARAM_FIELDS = ["b", "c", "AR", "S", "lam", "St", "lt", "Sf", "lf", "Xac",
                  "mass", "Ixx", "Iyy", "Izz", "Ixz",
@@ -112,6 +118,23 @@ class CollocConfig(ctypes.Structure):
         return d
 
 
+class IdentConfig(ctypes.Structure):
+    """kite_ident_config: the identification of the 21 aerodynamic coefficients."""
+    _fields_ = [
+        ("substeps", ctypes.c_int32), ("segment", ctypes.c_int32), ("iters", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("h", ctypes.c_double), ("Q", ctypes.c_double * 13), ("alpha", ctypes.c_double), ("lm0", ctypes.c_double),
+        ("tol", ctypes.c_double), ("lb_rel", ctypes.c_double * 21), ("ub_rel", ctypes.c_double * 21),
+    ]
+
+    def to_dict(self) -> dict:
+        d = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            d[name] = list(v) if hasattr(v, "__len__") else v
+        return d
+
+
 class MpcDiagnostic(ctypes.Structure):
     """msg/mpc_diagnostic.msg field order."""
     _fields_ = [("pos_error", ctypes.c_double), ("vel_error", ctypes.c_double), ("cost", ctypes.c_double),
@@ -180,6 +203,21 @@ _SIGNATURES = {
                                                      ctypes.c_void_p]),
     "kite_nmpc_jacobian_wind": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, _DP]),
     "kite_nmpc_set_wind_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]),
+    "kite_ident_default_config": (None, [ctypes.POINTER(IdentConfig)]),
+    "kite_ident_param_index": (ctypes.c_int, [ctypes.c_int32]),
+    "kite_nmpc_ident_sens": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+                                            ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, _DP]),
+    "kite_nmpc_ident_normal": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IdentConfig), ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, _DP, _DP,
+                                              _DP, _IP]),
+    "kite_nmpc_identify": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IdentConfig), ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_void_p, ctypes.c_int32, _DP, _DP, ctypes.c_void_p, _DP, _IP, _IP]),
+    "kite_nmpc_identify_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IdentConfig), ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    "kite_nmpc_ident_workspace_doubles": (ctypes.c_int64, [ctypes.POINTER(IdentConfig), ctypes.c_int32,
+                                                           ctypes.c_int32]),
     "kite_nmpc_plant_set_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "kite_nmpc_plant_set_wind": (ctypes.c_int, [ctypes.c_void_p, _DP]),
     "kite_nmpc_plant_step": (ctypes.c_int, [ctypes.c_void_p, _DP, _DP, ctypes.c_double, ctypes.c_double,
@@ -246,6 +284,36 @@ def load_properties(path: str = DEFAULT_PARAMS) -> KiteParams:
     return p
 
 
+# YAML keys of the 52 fields (kite_utils::LoadProperties, kite.cpp:7-76): the
+# field names in their sections, the tether length under its own key
+_YAML_SECTIONS = (("geometry", 0, 10), ("inertia", 10, 15), ("aerodynamic", 15, 46), ("tether", 46, 52))
+
+
+def save_properties(path: str, params_row, template: str = DEFAULT_PARAMS) -> None:
+    """Write a parameter file that ``load_properties`` reads back to the same 52
+    doubles bit for bit (the reference's ``umx_radian_id.yaml`` step,
+    kite_identification_test.cpp).  params_row: a ``KiteParams`` or 52 values;
+    the top-level scalar lines of ``template`` (its ``name:``) are carried over."""
+    v = params_row.as_array() if isinstance(params_row, KiteParams) else _f64(params_row).reshape(-1)
+    if v.size != len(_PARAM_FIELDS):
+        raise ValueError("52 parameter values expected")
+    head = []
+    if template:
+        with open(template) as f:
+            for line in f:
+                body = line.split("#", 1)[0].rstrip()
+                if body and not body[0].isspace() and ":" in body and body.split(":", 1)[1].strip():
+                    head.append(body)
+    out = ["# written by openkite_amd.save_properties"] + head
+    for sec, lo, hi in _YAML_SECTIONS:
+        out += ["", sec + ":"]
+        for i in range(lo, hi):
+            key = "length" if _PARAM_FIELDS[i] == "Lt" else _PARAM_FIELDS[i]
+            out.append("    %s: %r" % (key, float(v[i])))     # repr round-trips through strtod
+    with open(path, "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
 # perturb_params' default selection: what differs between two airframes of one
 # design (mass, inertias, aerodynamic coefficients); the geometry (b .. Xac) and
 # the tether (Lt .. rz) stay as they are
@@ -290,6 +358,48 @@ def default_config(**overrides) -> NmpcConfig:
         else:
             setattr(c, k, v)
     return c
+
+
+def ident_default_config(**overrides) -> IdentConfig:
+    """kite_ident_default_config: the reference's weights and boxes
+    (kite_identification_test.cpp:127-148, :193), h = 0.02, 4 substeps, one-step
+    segments, 12 evaluations."""
+    c = IdentConfig()
+    lib().kite_ident_default_config(ctypes.byref(c))
+    for k, v in overrides.items():
+        if not hasattr(c, k):
+            raise KeyError(k)
+        cur = getattr(c, k)
+        if hasattr(cur, "__len__"):
+            vv = np.broadcast_to(np.asarray(v, dtype=np.float64), (len(cur),))
+            for i, vi in enumerate(vv):
+                cur[i] = vi
+        else:
+            setattr(c, k, v)
+    return c
+
+
+def ident_param_index(j: int) -> int:
+    """kite_params field index of identified parameter j (-1 outside 0..20)."""
+    return int(lib().kite_ident_param_index(int(j)))
+
+
+def ident_workspace_doubles(config: IdentConfig, count: int, T: int) -> int:
+    """Workspace of ``BatchNMPC.identify_device`` in doubles."""
+    return _check(int(lib().kite_nmpc_ident_workspace_doubles(ctypes.byref(config), int(count), int(T))),
+                  "ident_workspace_doubles")
+
+
+@dataclass
+class IdentResult:
+    """``BatchNMPC.identify``: params (B, 52) the input rows with the 21
+    replaced, cost0 / cost the first and the final accepted cost, evals the
+    evaluations done, status the KITE_IDENT_* words."""
+    params: np.ndarray
+    cost0: np.ndarray
+    cost: np.ndarray
+    evals: np.ndarray
+    status: np.ndarray
 
 
 class BatchNMPC:
@@ -588,6 +698,78 @@ class BatchNMPC:
         v = lambda p: ctypes.c_void_p(p) if p else None
         _check(lib().kite_nmpc_plant_step_device(self._h, v(x13_ptr), v(u4_ptr), float(t0), float(h), int(steps),
                                                  int(substeps), v(status_ptr)), "plant_step_device")
+
+    # --- aerodynamic parameter identification ---------------------------------
+    def _ident_rows(self, params, count: int) -> np.ndarray:
+        """(1, 52) or (count, 52) rows of kite_params; None: the context's own."""
+        if params is None:
+            params = self.params
+        if isinstance(params, KiteParams):
+            params = params.as_array()
+        p = _f64(params)
+        if p.ndim == 1:
+            p = p.reshape(1, -1)
+        if p.ndim != 2 or p.shape[1] != len(_PARAM_FIELDS) or p.shape[0] not in (1, count):
+            raise ValueError("identification parameters: 52 values, one row or one per kite")
+        return p
+
+    def ident_sens(self, x13, u3, h: float, substeps: int = 4, params=None):
+        """One sample interval per item (kite_nmpc_ident_sens): x+ (count, 13) and
+        S = d x+ / d p (count, 13, 21, unscaled) with respect to ``IDENT_FIELDS``."""
+        x = _f64(x13).reshape(-1, 13); u = _f64(u3).reshape(-1, 3)
+        c = x.shape[0]
+        p = self._ident_rows(params, c)
+        xo = np.zeros((c, 13)); S = np.zeros((c, 13, IDENT_NP))
+        _check(lib().kite_nmpc_ident_sens(self._h, c, float(h), int(substeps), ctypes.c_void_p(p.ctypes.data),
+                                          p.shape[0], _p(x), _p(u), _p(xo), _p(S)), "ident_sens")
+        return xo, S
+
+    def ident_normal(self, X, U, p21, params=None, config: Optional[IdentConfig] = None):
+        """One evaluation of the identification's normal equations at the
+        parameter values p21 (B, 21) on the logs X (B, T+1, 13), U (B, T, 3):
+        (A (B, 21, 21), g (B, 21), cost (B,), status (B,)) in the scaled variables."""
+        cfg = config if config is not None else ident_default_config()
+        X = _f64(X); U = _f64(U)
+        B, T = U.shape[0], U.shape[1]
+        if X.shape != (B, T + 1, 13) or U.shape != (B, T, 3):
+            raise ValueError("logs: X (B, T+1, 13), U (B, T, 3)")
+        p = self._ident_rows(params, B)
+        q = _f64(p21).reshape(B, IDENT_NP)
+        A = np.zeros((B, IDENT_NP, IDENT_NP)); g = np.zeros((B, IDENT_NP)); cost = np.zeros(B)
+        st = np.zeros(B, dtype=np.int32)
+        _check(lib().kite_nmpc_ident_normal(self._h, ctypes.byref(cfg), B, T, ctypes.c_void_p(p.ctypes.data),
+                                            p.shape[0], _p(q), _p(X), _p(U), _p(A), _p(g), _p(cost),
+                                            st.ctypes.data_as(_IP)), "ident_normal")
+        return A, g, cost, st
+
+    def identify(self, X, U, params=None, config: Optional[IdentConfig] = None) -> IdentResult:
+        """Fit the 21 aerodynamic coefficients (``IDENT_FIELDS``) of every kite to
+        its log X (B, T+1, 13), U (B, T, 3) (kite_nmpc_identify).  params: the
+        kites' rows (52 values, one for all or (B, 52)), whose 21 are the start
+        and the centre of the box; None: the context's own."""
+        cfg = config if config is not None else ident_default_config()
+        X = _f64(X); U = _f64(U)
+        B, T = U.shape[0], U.shape[1]
+        if X.shape != (B, T + 1, 13) or U.shape != (B, T, 3):
+            raise ValueError("logs: X (B, T+1, 13), U (B, T, 3)")
+        p = self._ident_rows(params, B)
+        out = np.zeros((B, len(_PARAM_FIELDS))); c2 = np.zeros((B, 2))
+        ev = np.zeros(B, dtype=np.int32); st = np.zeros(B, dtype=np.int32)
+        _check(lib().kite_nmpc_identify(self._h, ctypes.byref(cfg), B, T, ctypes.c_void_p(p.ctypes.data), p.shape[0],
+                                        _p(X), _p(U), ctypes.c_void_p(out.ctypes.data), _p(c2),
+                                        ev.ctypes.data_as(_IP), st.ctypes.data_as(_IP)), "identify")
+        return IdentResult(out, c2[:, 0].copy(), c2[:, 1].copy(), ev, st)
+
+    def identify_device(self, config: IdentConfig, count: int, T: int, params_ptr: int, nparams: int, X_ptr: int,
+                        U_ptr: int, params_out_ptr: int, cost2_ptr: int = 0, evals_ptr: int = 0, status_ptr: int = 0,
+                        workspace_ptr: int = 0):
+        """identify on device pointers (kite_nmpc_identify_device): 2 * iters
+        launches on the context stream, nothing allocated, copied or awaited;
+        the workspace holds ``ident_workspace_doubles`` doubles."""
+        v = lambda p: ctypes.c_void_p(p) if p else None
+        _check(lib().kite_nmpc_identify_device(self._h, ctypes.byref(config), int(count), int(T), v(params_ptr),
+                                               int(nparams), v(X_ptr), v(U_ptr), v(params_out_ptr), v(cost2_ptr),
+                                               v(evals_ptr), v(status_ptr), v(workspace_ptr)), "identify_device")
 
     def rk4_sens(self, x15, u4, tf: float, M: int):
         x = _f64(x15).reshape(-1, 15); u = _f64(u4).reshape(-1, 4)
