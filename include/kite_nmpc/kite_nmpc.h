@@ -52,7 +52,10 @@ extern "C" {
                                       (kite_nmpc_windekf_step[_device], _jacobian_wind,
                                       _set_wind_device, KITE_EKF_*) and the parameter
                                       identification (kite_nmpc_identify[_device],
-                                      _ident_normal, _ident_sens, KITE_IDENT_*)   */
+                                      _ident_normal, _ident_sens, KITE_IDENT_*) and
+                                      the per-kite controller models
+                                      (kite_nmpc_set_params[_device], _get_params,
+                                      KITE_PARAMS_REJECTED)                       */
 #define KITE_PATH_MAX_HARMONICS 8 /* Fourier path: harmonics per axis              */
 
 /* ---- error codes ------------------------------------------------------ */
@@ -402,6 +405,48 @@ int kite_nmpc_jacobian_wind(kite_nmpc_ctx* ctx, int32_t count, const double* x13
  * returns to the reference model.  wmax <= 0 or non-finite, stride < 3:
  * KITE_EINVAL.                                                              */
 int kite_nmpc_set_wind_device(kite_nmpc_ctx* ctx, const double* d_wind, int32_t stride, double wmax);
+
+/* ---- per-kite controller models (build extension; additive, no version change)
+ * The model of the controller's predictions, per kite: the batch dimension
+ * "one airframe per instance", and the way identified parameters
+ * (kite_nmpc_identify_device) reach a running controller without leaving the
+ * device.
+ *   count == B     kite b's model is params[b]
+ *   count == 1     one model for every kite (passed to the kernels as the
+ *                  creation model is; also the form of a batch of one)
+ *   params == NULL back to the creation model
+ * Scope, as kite_nmpc_set_wind's: the model is used by every prediction of
+ * kite_nmpc_step[_device] -- cold-start simulation, delay compensation,
+ * sensitivities, defects -- with and without a controller wind, at every
+ * horizon and with every qp_kernel.  The item-wise entry points (dynamics,
+ * jacobian, predict, rk4_sens, colloc_eval, ident_*), both EKFs and the
+ * plant's default keep the creation model.  Rows equal to the creation row
+ * give the creation model's outputs bit for bit.
+ * A row must be a model (kite_nmpc_plant_set_params' rule: every field finite,
+ * mass > 0, an invertible inertia, finite derived constants): one bad row is
+ * KITE_EINVAL and the previous setting stays whole.  Any other count:
+ * KITE_EINVAL.  count == B with cfg.sens_fp32 = 1 (and B > 1): KITE_ESTATE,
+ * the fp32 sensitivity path holds one model.  The step graph is re-captured
+ * when the call changes which kernels run or a model they hold by value
+ * (count == 1, NULL, the first count == B), not when it refreshes the rows of
+ * a per-kite setting.                                                        */
+#define KITE_PARAMS_REJECTED 1   /* status bit: the row is no model, the kite keeps its previous one */
+int kite_nmpc_set_params(kite_nmpc_ctx* ctx, const kite_params* params, int32_t count);
+/* The count == B form from device memory (d_params52: B x 52 doubles, e.g. the
+ * params_out of kite_nmpc_identify_device), asynchronous on the context
+ * stream: one small kernel forms every kite's constants with the host's
+ * arithmetic, bit for bit.  The device cannot refuse a row: a kite whose row
+ * is no model keeps its previous one -- on the first call the model in force
+ * until then, i.e. the creation model unless a count == 1 model was set --
+ * and has KITE_PARAMS_REJECTED in d_status (B words, nullable, written on
+ * every call, not OR-ed); the other kites are unaffected.  count != B or a
+ * NULL row pointer: KITE_EINVAL; cfg.sens_fp32 = 1: KITE_ESTATE.  Only the
+ * first call (the switch to per-kite kernels) re-captures the step graph.    */
+int kite_nmpc_set_params_device(kite_nmpc_ctx* ctx, const double* d_params52, int32_t count, int32_t* d_status);
+/* The B rows in force (host pointer, B x kite_params): what the setters above
+ * left, the creation row B times when none was called.  Waits for the context
+ * stream when a per-kite setting is in force.                                 */
+int kite_nmpc_get_params(kite_nmpc_ctx* ctx, kite_params* out);
 
 /* ---- aerodynamic parameter identification (additive, no version change) ----
  * src/kite_control/kite_identification_test.cpp: fit the 21 aerodynamic

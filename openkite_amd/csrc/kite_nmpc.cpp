@@ -71,6 +71,13 @@ struct kite_nmpc_ctx {
     double *Htl = nullptr, *Hab = nullptr, *Hbb = nullptr;
     double* wind = nullptr;        // per-kite world-frame wind B x 3 (kite_nmpc_set_wind)
     bool has_wind = false;         // a nonzero wind is set: the WIND kernels run
+    // the model of the step's predictions (kite_nmpc_set_params[_device]); mc and
+    // params stay the creation model, which every item-wise entry point keeps
+    int model_mode = 0;            // 0: mc; 1: model_mc1 for all (kernel argument); 2: the table
+    ModelConst model_mc1;          // mode 1
+    kite_params model_params1;     // mode 1: its row (kite_nmpc_get_params)
+    double* model_tab = nullptr;   // mode 2: [B][kModelTableStride] constants per kite, allocated once
+    double* model_rows = nullptr;  // mode 2: B x 52, the kite_params rows in force, allocated once
     // plant simulator (plant_kernels.hip; kite_nmpc_plant_*)
     int plant_count = 0;           // 0: the controller's own model (mc); 1: plant_mc1 for all; B: plant_mc
     ModelConst plant_mc1;          // count == 1
@@ -290,7 +297,7 @@ void free_ctx(kite_nmpc_ctx* ctx) {
     double** bufs[] = {&ctx->X, &ctx->U, &ctx->x0, &ctx->AB, &ctx->DEF, &ctx->Hs, &ctx->hs,
                        &ctx->Cr, &ctx->cl, &ctx->cu, &ctx->hmax, &ctx->u0, &ctx->diag, &ctx->kkt,
                        &ctx->scratch, &ctx->Htl, &ctx->Hab, &ctx->Hbb, &ctx->wstep, &ctx->wind,
-                       &ctx->plant_mc, &ctx->plant_wind};
+                       &ctx->plant_mc, &ctx->plant_wind, &ctx->model_tab, &ctx->model_rows};
     for (double** p : bufs) if (*p) { (void)hipFree(*p); *p = nullptr; }
     if (ctx->dconst) { (void)hipFree(ctx->dconst); ctx->dconst = nullptr; }
     if (ctx->status) { (void)hipFree(ctx->status); ctx->status = nullptr; }
@@ -341,10 +348,14 @@ int run_step(kite_nmpc_ctx* ctx, const double* x0) {
     const double* wind = ctx->has_wind ? ctx->wind : nullptr;
     if (ctx->cold_dirty) HIP_TRY(hipMemsetAsync(ctx->order + 2 * B + 1, 0, sizeof(int32_t), s));
     ctx->cold_dirty = true;
-    HIP_TRY(kite::launch_prologue(ctx->mc, ctx->rc, B, ctx->warm ? 1 : 0, x0, ctx->X, ctx->U, ctx->status,
-                                  wind, ctx->order + 2 * B + 1, s));
+    // the model of this step's predictions: the creation model, one set model
+    // (both kernel arguments) or the per-kite table
+    const ModelConst& mc = ctx->model_mode == 1 ? ctx->model_mc1 : ctx->mc;
+    const double* mct = ctx->model_mode == 2 ? ctx->model_tab : nullptr;
+    HIP_TRY(kite::launch_prologue(mc, ctx->rc, B, ctx->warm ? 1 : 0, x0, ctx->X, ctx->U, ctx->status,
+                                  wind, ctx->order + 2 * B + 1, mct, s));
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
-    HIP_TRY(kite::launch_rk4_sens(ctx->mc, ctx->rc, B, ctx->X, ctx->U, ctx->AB, ctx->DEF, wind, s));
+    HIP_TRY(kite::launch_rk4_sens(mc, ctx->rc, B, ctx->X, ctx->U, ctx->AB, ctx->DEF, wind, mct, s));
     if (ev) HIP_TRY(hipEventRecord(ev[2], s));
     if (!ctx->ric)
         HIP_TRY(kite::launch_condense(ctx->rc, B, ctx->X, ctx->U, ctx->AB, ctx->DEF, ctx->Hs, ctx->hs, ctx->Cr,
@@ -1256,6 +1267,99 @@ int kite_nmpc_set_wind_device(kite_nmpc_ctx* ctx, const double* d_wind, int32_t 
         ctx->has_wind = true;
         ++ctx->graph_gen;
     }
+    return KITE_OK;
+}
+
+// ---- per-kite controller models (k_model_const, rti_kernels.hip) -------------
+extern "C++" {
+namespace {
+// table and rows in force, allocated once (the captured step holds the table's address)
+int ensure_model_table(kite_nmpc_ctx* ctx) {
+    const size_t B = ctx->B;
+    if (!ctx->model_tab) HIP_TRY(hipMalloc(&ctx->model_tab, B * kite::kModelTableStride * sizeof(double)));
+    if (!ctx->model_rows) HIP_TRY(hipMalloc(&ctx->model_rows, B * 52 * sizeof(double)));
+    return KITE_OK;
+}
+// every kite's table row from the model in force (mode 0 or 1): what a kite
+// keeps when the device setter rejects its row
+int fill_model_table(kite_nmpc_ctx* ctx) {
+    const bool one = ctx->model_mode == 1;
+    const kite_params& p = one ? ctx->model_params1 : ctx->params;
+    HIP_TRY(kite::launch_model_fill(one ? ctx->model_mc1 : ctx->mc, reinterpret_cast<const double*>(&p), ctx->B,
+                                    ctx->model_tab, ctx->model_rows, ctx->stream));
+    return KITE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int kite_nmpc_set_params(kite_nmpc_ctx* ctx, const kite_params* params, int32_t count) {
+    if (!ctx) return KITE_EINVAL;
+    if (!params) {                                   // back to the creation model
+        ctx->model_mode = 0;
+        ++ctx->graph_gen;                            // captured kernels hold the model by value
+        return KITE_OK;
+    }
+    if (count != 1 && count != ctx->B) return KITE_EINVAL;
+    if (count == 1) {                                // also a batch of one
+        ModelConst m;
+        if (!plant_params_ok(params[0], &m)) return KITE_EINVAL;
+        ctx->model_mc1 = m;
+        ctx->model_params1 = params[0];
+        ctx->model_mode = 1;
+        ++ctx->graph_gen;
+        return KITE_OK;
+    }
+    if (ctx->cfg.sens_fp32) return KITE_ESTATE;      // k_defects and the fp32 kernel hold one model
+    for (int32_t b = 0; b < count; ++b) {
+        ModelConst m;
+        if (!plant_params_ok(params[b], &m)) return KITE_EINVAL;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    { const int rc = ensure_model_table(ctx); if (rc) return rc; }
+    // the validated rows become the rows in force; the table comes from them on
+    // the device, by the kernel the device setter runs (ordered with the steps
+    // on the context stream, synchronous on it)
+    HIP_TRY(hipMemcpyAsync(ctx->model_rows, params, (size_t)count * sizeof(kite_params), hipMemcpyHostToDevice,
+                           ctx->stream));
+    HIP_TRY(kite::launch_model_const(ctx->B, ctx->model_rows, ctx->model_tab, ctx->model_rows, nullptr, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->model_mode != 2) {
+        ctx->model_mode = 2;
+        ++ctx->graph_gen;                            // the table selects other kernels
+    }
+    return KITE_OK;
+}
+
+int kite_nmpc_set_params_device(kite_nmpc_ctx* ctx, const double* d_params52, int32_t count, int32_t* d_status) {
+    if (!ctx || !d_params52 || count != ctx->B) return KITE_EINVAL;
+    if (ctx->cfg.sens_fp32) return KITE_ESTATE;
+    HIP_TRY(hipSetDevice(ctx->device));
+    { const int rc = ensure_model_table(ctx); if (rc) return rc; }
+    if (ctx->model_mode != 2) {
+        // the switch to the table: a kite whose row is rejected keeps the model it had
+        const int rc = fill_model_table(ctx);
+        if (rc) return rc;
+    }
+    HIP_TRY(kite::launch_model_const(ctx->B, d_params52, ctx->model_tab, ctx->model_rows, d_status, ctx->stream));
+    // the captured step reads the table when it runs: a refresh of the values
+    // needs no new graph, only the switch to the per-kite kernels does
+    if (ctx->model_mode != 2) {
+        ctx->model_mode = 2;
+        ++ctx->graph_gen;
+    }
+    return KITE_OK;
+}
+
+int kite_nmpc_get_params(kite_nmpc_ctx* ctx, kite_params* out) {
+    if (!ctx || !out) return KITE_EINVAL;
+    if (ctx->model_mode != 2) {
+        for (int b = 0; b < ctx->B; ++b) out[b] = ctx->model_mode == 1 ? ctx->model_params1 : ctx->params;
+        return KITE_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(out, ctx->model_rows, (size_t)ctx->B * sizeof(kite_params), hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return KITE_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "kite_model.hpp"
+#include "kite_model_dp.hpp"
 #include "rti_kernels.hpp"
 #include "rti_device.hpp"
 
@@ -254,6 +255,55 @@ __global__ __launch_bounds__(64) void k_prologue_cold(ModelConst P, RtiConst C, 
     }
 }
 
+// Per-kite model constants (kite_nmpc_set_params[_device]): the table mct is
+// kite-major, [B][MCT_STRIDE] doubles -- a kite's ModelConst (47) and one pad,
+// 384-byte rows.  Every wave that needs constants needs ONE kite's row, so the
+// row address is wave-uniform and the row arrives by scalar loads into the
+// SGPRs that hold the kernel-argument ModelConst of the homogeneous kernels.
+// (k_plant's store is field-major because there a LANE is a kite.)
+constexpr int MCT_STRIDE = kModelTableStride;
+static_assert(kModelConstDoubles < MCT_STRIDE, "a table row holds a ModelConst and a pad");
+__device__ __forceinline__ ModelConst model_row(const double* __restrict__ mct, int b) {
+    const double* r = mct + (size_t)b * MCT_STRIDE;
+    ModelConst P;
+    double* g = reinterpret_cast<double*>(&P);
+#pragma unroll
+    for (int i = 0; i < kModelConstDoubles; ++i) g[i] = r[i];
+    return P;
+}
+
+// k_prologue and k_prologue_cold with a model per kite: the kite's table row
+// instead of the kernel argument (the wave is one kite: a wave-uniform row).
+__global__ __launch_bounds__(64) void k_prologue_pk(const double* __restrict__ mct, RtiConst C, int B, int warm,
+                                                    const double* __restrict__ x0in,
+                                                    double* __restrict__ X, double* __restrict__ U,
+                                                    int32_t* __restrict__ status, const double* __restrict__ wind) {
+    __shared__ double sx0[NX];
+    __shared__ double sUv[KITE_NMAX];
+    __shared__ int sWarm;
+    if ((int)blockIdx.x >= B) return;
+    const ModelConst P = model_row(mct, blockIdx.x);
+    prologue_kite<true>(P, C, blockIdx.x, warm, x0in, X, U, status, wind, nullptr, sx0, sUv, &sWarm);
+}
+__global__ __launch_bounds__(64) void k_prologue_cold_pk(const double* __restrict__ mct, RtiConst C,
+                                                         const double* __restrict__ x0in,
+                                                         double* __restrict__ X, double* __restrict__ U,
+                                                         int32_t* __restrict__ status,
+                                                         const double* __restrict__ wind,
+                                                         const int32_t* __restrict__ cold, int B) {
+    __shared__ double sx0[NX];
+    __shared__ double sUv[KITE_NMAX];
+    __shared__ int sWarm;
+    const int n = min(cold[0], B);
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const int b = __builtin_amdgcn_readfirstlane(cold[1 + i]);
+        if (b < 0 || b >= B) continue;      // block-uniform
+        const ModelConst P = model_row(mct, b);
+        prologue_kite<true>(P, C, b, 1, x0in, X, U, status, wind, nullptr, sx0, sUv, &sWarm);
+        __syncthreads();
+    }
+}
+
 // ---------------------------------------------------------------------------
 // k_rk4_sens2: the sensitivity kernel.  RK4 (kitemath.cpp:36-51) with M
 // substeps of the 13-state kite ODE under constant u_k, carried with forward
@@ -281,48 +331,29 @@ __global__ __launch_bounds__(RK2_T, 1) void k_rk4_sens2(ModelConst P, int B, int
     const int b = blockIdx.x * (RK2_T / 8) + (threadIdx.x >> 3);
     const int k = blockIdx.y;
     if (b >= B) return;
-    const double* xk = X + ((size_t)b * (N + 1) + k) * NX;
-    const double* uk = U + ((size_t)b * N + k) * NU;
-    const int d0 = 2 * d, d1 = 2 * d + 1;
-    const ST one = ST(1), zero = ST(0), hs = ST(h);
-    DT x[NK], u[NKU];
-#pragma unroll
-    for (int i = 0; i < NK; ++i) x[i] = DT(ST(xk[i]), d0 == i ? one : zero, d1 == i ? one : zero);
-#pragma unroll
-    for (int j = 0; j < NKU; ++j) u[j] = DT(ST(uk[j]), d0 == NK + j ? one : zero, d1 == NK + j ? one : zero);
-#pragma unroll 1
-    for (int m = 0; m < M; ++m) {
-        DT xs[NK], acc[NK], kv[NK];
-#pragma unroll
-        for (int i = 0; i < NK; ++i) { xs[i] = x[i]; acc[i] = x[i]; }
-#pragma unroll 1
-        for (int st = 0; st < 4; ++st) {
-            kite_rhs<DT, WIND>(P, xs, u, kv, WIND ? wind + 3 * b : nullptr);
-            const ST wa = (st == 0 || st == 3) ? hs / ST(6) : hs / ST(3);
-            const ST wn = (st < 2) ? ST(0.5) * hs : hs;
-#pragma unroll
-            for (int i = 0; i < NK; ++i) {
-                acc[i] = rk_axpy<DT, ST>(wa, kv[i], acc[i]);
-                xs[i] = rk_axpy<DT, ST>(wn, kv[i], x[i]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NK; ++i) x[i] = acc[i];
-    }
-    double* ab = AB + ((size_t)b * N + k) * (NK * 16);
-#pragma unroll
-    for (int i = 0; i < NK; ++i) {
-        ab[i * 16 + d0] = (double)x[i].a;
-        ab[i * 16 + d1] = (double)x[i].b;
-    }
-    if constexpr (std::is_same<ST, double>::value) {
-        if (d == 0) {
-            const double* xn = X + ((size_t)b * (N + 1) + k + 1) * NX;
-            double* df = DEF + ((size_t)b * N + k) * NK;
-#pragma unroll
-            for (int i = 0; i < NK; ++i) df[i] = x[i].v - xn[i];
-        }
-    }
+#include "rk4_sens2_body.inc"
+}
+
+// k_rk4_sens2 with a model per kite (PERKITE = true only).  The homogeneous
+// block holds 8 kites x 8 direction pairs, which would make the 47 constants
+// lane-varying: 94 more VGPRs in a kernel that has none to spare.  Here a
+// block is ONE kite: 8 intervals x 8 direction pairs, b = blockIdx.x,
+// k = 8 blockIdx.y + lane / 8, grid (B, ceil(N / 8)); lanes with k >= N
+// leave.  The kite's row and its wind are wave-uniform.  Per (kite, interval,
+// direction) the arithmetic is the same included body.
+template <class DT, class ST, bool WIND, bool PERKITE>
+__global__ __launch_bounds__(RK2_T, 1) void k_rk4_sens2(const double* __restrict__ mct, int B, int N, int M, double h,
+                                                        const double* __restrict__ X,
+                                                        const double* __restrict__ U,
+                                                        double* __restrict__ AB, double* __restrict__ DEF,
+                                                        const double* __restrict__ wind) {
+    static_assert(PERKITE, "the homogeneous kernel is the three-parameter k_rk4_sens2");
+    const int d = threadIdx.x & 7;
+    const int b = blockIdx.x;
+    const int k = blockIdx.y * (RK2_T / 8) + (threadIdx.x >> 3);
+    if (b >= B || k >= N) return;
+    const ModelConst P = model_row(mct, b);
+#include "rk4_sens2_body.inc"
 }
 
 // Latency form for small batches (B <= RK1_MAXB, fp64): ONE tangent per lane,
@@ -394,6 +425,60 @@ __global__ __launch_bounds__(64, 2) void k_defects(ModelConst P, int B, int N, i
     else rk4_primal(P, x0, u4, h, M, xo);
     double* df = DEF + ((size_t)b * N + k) * NK;
     for (int i = 0; i < NK; ++i) df[i] = xo[i] - xk[NX + i];
+}
+
+// ---------------------------------------------------------------------------
+// k_model_const: the per-kite table from kite_params rows on the device
+// (kite_nmpc_set_params[_device]), one lane per kite.  A row that is a model
+// (the plant setter's rule: every field finite, mass > 0, an invertible
+// inertia, finite derived constants) becomes the kite's table row -- the
+// unfused arithmetic of ident_model_const, the host's constants bit for bit --
+// and its row in force (rows, B x 52).  Any other row leaves both as they are
+// and is reported (KITE_PARAMS_REJECTED); status is written for every kite.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_model_const(int B, const double* rows52, double* mct, double* rows,
+                                                    int32_t* status) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double* r = rows52 + (size_t)b * 52;
+    double row[52];
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 52; ++i) { row[i] = r[i]; ok = ok && isfinite(row[i]); }
+    const double mass = row[10], Ixx = row[11], Iyy = row[12], Izz = row[13], Ixz = row[14];
+    ok = ok && mass > 0.0 && Ixx * Izz - Ixz * Ixz != 0.0 && Iyy != 0.0;
+    const ModelConst m = ident_model_const(row, nullptr);
+    const double* g = reinterpret_cast<const double*>(&m);
+#pragma unroll
+    for (int i = 0; i < kModelConstDoubles; ++i) ok = ok && isfinite(g[i]);
+    if (ok) {
+        double* t = mct + (size_t)b * MCT_STRIDE;
+#pragma unroll
+        for (int i = 0; i < kModelConstDoubles; ++i) t[i] = g[i];
+#pragma unroll
+        for (int i = kModelConstDoubles; i < MCT_STRIDE; ++i) t[i] = 0.0;
+        double* o = rows + (size_t)b * 52;
+#pragma unroll
+        for (int i = 0; i < 52; ++i) o[i] = row[i];
+    }
+    if (status) status[b] = ok ? 0 : KITE_PARAMS_REJECTED;
+}
+// every table row and row in force from one model (the switch to the table)
+struct ParamsRow { double v[52]; };
+__global__ __launch_bounds__(64) void k_model_fill(ModelConst P, ParamsRow R, int B, double* __restrict__ mct,
+                                                   double* __restrict__ rows) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double* g = reinterpret_cast<const double*>(&P);
+    double* t = mct + (size_t)b * MCT_STRIDE;
+#pragma unroll
+    for (int i = 0; i < kModelConstDoubles; ++i) t[i] = g[i];
+#pragma unroll
+    for (int i = kModelConstDoubles; i < MCT_STRIDE; ++i) t[i] = 0.0;
+    double* o = rows + (size_t)b * 52;
+#pragma unroll
+    for (int i = 0; i < 52; ++i) o[i] = R.v[i];
 }
 
 // ---------------------------------------------------------------------------
@@ -2076,19 +2161,39 @@ __global__ __launch_bounds__(64, 2) void k_closest_point(RtiConst C, int count, 
 // ---------------------------------------------------------------------------
 hipError_t launch_prologue(const ModelConst& P, const RtiConst& C, int B, int warm, const double* x0,
                            double* X, double* U, int32_t* status, const double* wind, int32_t* cold,
-                           hipStream_t s) {
+                           const double* mct, hipStream_t s) {
     constexpr int PRO_COLD_GRID = 256;
     if (warm && !(C.delay > 0.0)) {
+        // (k_prologue_warm compiles no simulation: it needs no model)
         hipLaunchKernelGGL(k_prologue_warm, dim3(B), dim3(64), 0, s, P, C, B, x0, X, U, status, cold);
-        hipLaunchKernelGGL(k_prologue_cold, dim3(B < PRO_COLD_GRID ? B : PRO_COLD_GRID), dim3(64), 0, s, P, C,
-                           x0, X, U, status, wind, cold, B);
+        if (mct)
+            hipLaunchKernelGGL(k_prologue_cold_pk, dim3(B < PRO_COLD_GRID ? B : PRO_COLD_GRID), dim3(64), 0, s, mct,
+                               C, x0, X, U, status, wind, cold, B);
+        else
+            hipLaunchKernelGGL(k_prologue_cold, dim3(B < PRO_COLD_GRID ? B : PRO_COLD_GRID), dim3(64), 0, s, P, C,
+                               x0, X, U, status, wind, cold, B);
+    } else if (mct) {
+        hipLaunchKernelGGL(k_prologue_pk, dim3(B), dim3(64), 0, s, mct, C, B, warm, x0, X, U, status, wind);
     } else {
         hipLaunchKernelGGL(k_prologue, dim3(B), dim3(64), 0, s, P, C, B, warm, x0, X, U, status, wind);
     }
     return hipGetLastError();
 }
 hipError_t launch_rk4_sens(const ModelConst& P, const RtiConst& C, int B, const double* X, const double* U,
-                           double* AB, double* DEF, const double* wind, hipStream_t s) {
+                           double* AB, double* DEF, const double* wind, const double* mct, hipStream_t s) {
+    if (mct) {
+        // a model per kite: always the one-kite-per-wave Dual2 kernel (it agrees
+        // with k_rk4_sens1 bit for bit, so a kite's result does not depend on B)
+        if (C.sens_fp32) return hipErrorInvalidValue;       // refused by the setters
+        const dim3 gridk(B, (C.N + RK2_T / 8 - 1) / (RK2_T / 8));
+        if (wind)
+            hipLaunchKernelGGL((k_rk4_sens2<Dual2, double, true, true>), gridk, dim3(RK2_T), 0, s, mct, B, C.N, C.M,
+                               C.h, X, U, AB, DEF, wind);
+        else
+            hipLaunchKernelGGL((k_rk4_sens2<Dual2, double, false, true>), gridk, dim3(RK2_T), 0, s, mct, B, C.N, C.M,
+                               C.h, X, U, AB, DEF, nullptr);
+        return hipGetLastError();
+    }
     const dim3 grid2((B + RK2_T / 8 - 1) / (RK2_T / 8), C.N);
     if (C.sens_fp32) {
         if (wind)
@@ -2110,6 +2215,18 @@ hipError_t launch_rk4_sens(const ModelConst& P, const RtiConst& C, int B, const 
             hipLaunchKernelGGL((k_rk4_sens2<Dual2, double>), grid2, dim3(RK2_T), 0, s, P, B, C.N, C.M, C.h, X, U,
                                AB, DEF, nullptr);
     }
+    return hipGetLastError();
+}
+hipError_t launch_model_fill(const ModelConst& P, const double* row52, int B, double* mct, double* rows,
+                             hipStream_t s) {
+    ParamsRow R;
+    for (int i = 0; i < 52; ++i) R.v[i] = row52[i];
+    hipLaunchKernelGGL(k_model_fill, dim3((B + 63) / 64), dim3(64), 0, s, P, R, B, mct, rows);
+    return hipGetLastError();
+}
+hipError_t launch_model_const(int B, const double* d_rows52, double* mct, double* rows, int32_t* status,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(k_model_const, dim3((B + 63) / 64), dim3(64), 0, s, B, d_rows52, mct, rows, status);
     return hipGetLastError();
 }
 hipError_t launch_condense(const RtiConst& C, int B, const double* X, const double* U, const double* AB,
@@ -2247,7 +2364,7 @@ hipError_t launch_rk4_sens_items(const ModelConst& P, int sens_fp32, int count, 
     hipLaunchKernelGGL(k_sens_items_stage, dim3((count * 2 * NX + 63) / 64), dim3(64), 0, s, count, x, X2);
     RtiConst C{};
     C.N = 1; C.M = M; C.h = h; C.sens_fp32 = sens_fp32;
-    hipError_t e = launch_rk4_sens(P, C, count, X2, u, AB, DEF, nullptr, s);
+    hipError_t e = launch_rk4_sens(P, C, count, X2, u, AB, DEF, nullptr, nullptr, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_sens_items_expand, dim3((count * NX + 63) / 64), dim3(64), 0, s, count, M, h, x, u, AB, DEF,
                        xo, A, Bm);

@@ -76,11 +76,25 @@ hipError_t launch_qp_ric(const RtiConst& C, const RicConst& R, const RtiConst* C
 // reference model, no wind; kite_model.hpp kite_rhs<T, WIND>)
 // cold: B + 1 ints, the prologue's cold-restart list (count first; zero on
 // entry -- k_qp_order empties it every step)
+// mct: per-kite model constants, kite-major [B][kModelTableStride] doubles (a
+// kite's ModelConst and a pad), or nullptr: every kite takes P (kernel
+// argument).  With a table the sensitivities are fp64 only (C.sens_fp32 == 0).
 hipError_t launch_prologue(const ModelConst& P, const RtiConst& C, int B, int warm, const double* x0,
                            double* X, double* U, int32_t* status, const double* wind, int32_t* cold,
-                           hipStream_t s);
+                           const double* mct, hipStream_t s);
 hipError_t launch_rk4_sens(const ModelConst& P, const RtiConst& C, int B, const double* X, const double* U,
-                           double* AB, double* DEF, const double* wind, hipStream_t s);
+                           double* AB, double* DEF, const double* wind, const double* mct, hipStream_t s);
+constexpr int kModelTableStride = 48;
+// every row of the table mct and of the rows in force (rows, B x 52) from one
+// model: its constants P and its kite_params row52 (host pointer)
+hipError_t launch_model_fill(const ModelConst& P, const double* row52, int B, double* mct, double* rows,
+                             hipStream_t s);
+// the table from B kite_params rows in device memory (k_model_const): a row
+// that is a model replaces the kite's table row and row in force, any other
+// keeps both; status: B words (nullable), KITE_PARAMS_REJECTED per kite,
+// written on every call.  d_rows52 may be `rows` itself.
+hipError_t launch_model_const(int B, const double* d_rows52, double* mct, double* rows, int32_t* status,
+                              hipStream_t s);
 hipError_t launch_condense(const RtiConst& C, int B, const double* X, const double* U, const double* AB,
                            const double* DEF, double* Hs, double* hs, double* Cr, double* cl, double* cu,
                            double* hmax, int tiled, double* Htl, double* Hab, double* Hbb, hipStream_t s);

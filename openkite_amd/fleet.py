@@ -27,6 +27,12 @@ One step of a fleet of kites on one rank:
          (kite_nmpc_plant_step_device), and measures that state; theta and
          thetadot still come from the plan's node 1 (nmpf_node.cpp:220).
 
+  adapt  with ``recorder`` and ``adapt`` (an ``IdentConfig``): each time the
+         flight log is full, before the RTI, every kite's 21 aerodynamic
+         coefficients are identified from it (kite_nmpc_identify_device) and
+         become that kite's controller model (kite_nmpc_set_params_device),
+         all on the stream.
+
 The stepper does the arithmetic; ``GpuStepper`` drives libkite_nmpc.so on
 device tensors.  Tests plug a CPU oracle stepper into the same loop to check
 the sharded multi-rank flow against the unsharded batch.
@@ -69,6 +75,22 @@ class GpuStepper:
         ``wind.stride(0)`` doubles apart, components contiguous)."""
         assert wind.dtype == torch.float64 and wind.stride(1) == 1
         self.ctx.set_wind_device(wind.data_ptr(), wind.stride(0), wmax)
+
+    def set_params_device(self, rows, status=None):
+        """The controller's per-kite models from a contiguous (B, 52) device
+        tensor of kite_params rows; status (B,) int32 receives the
+        KITE_PARAMS_* words."""
+        assert rows.dtype == torch.float64 and rows.is_contiguous() and rows.shape[1] == 52
+        self.ctx.set_params_device(rows.data_ptr(), rows.shape[0], status.data_ptr() if status is not None else 0)
+
+    def get_params(self):
+        """The (B, 52) rows in force, on the host."""
+        return self.ctx.get_params()
+
+    def identify(self, config, T, rows, X, U, out, cost2, evals, status, ws):
+        """kite_nmpc_identify_device on device tensors, a row per kite."""
+        self.ctx.identify_device(config, rows.shape[0], T, rows.data_ptr(), rows.shape[0], X.data_ptr(), U.data_ptr(),
+                                 out.data_ptr(), cost2.data_ptr(), evals.data_ptr(), status.data_ptr(), ws.data_ptr())
 
 
 class GpuPlant:
@@ -177,9 +199,11 @@ class FleetLoop:
 
     def __init__(self, stepper, x0: torch.Tensor, N: int, dt: float, ekf: bool = False, ekf_substeps: int = 5,
                  covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None,
-                 plant=None, wind_ekf: bool = False, wind_max: float = 20.0, recorder=None):
+                 plant=None, wind_ekf: bool = False, wind_max: float = 20.0, recorder=None, adapt=None):
         if ekf and wind_ekf:
             raise ValueError("ekf and wind_ekf are two estimators: choose one")
+        if adapt is not None and recorder is None:
+            raise ValueError("adapt identifies from a flight log: give the loop a recorder")
         B = x0.shape[0]
         dev = x0.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -228,6 +252,24 @@ class FleetLoop:
         # a ``FlightRecorder``: the state handed to the controller and the control
         # applied, one period per step, until it is full
         self.recorder = recorder
+        # adapt (an ``IdentConfig``): each time the recorder is full the kites'
+        # 21 aerodynamic coefficients are identified from it and become the
+        # controller's per-kite models, all on the stream (``_adapt``)
+        self.adapt = adapt
+        self.adapt_count = 0
+        if adapt is not None:
+            from . import nmpc
+            if recorder.B != B:
+                raise ValueError(f"the recorder logs {recorder.B} kites, the loop flies {B}")
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.model_rows = torch.from_numpy(np.ascontiguousarray(stepper.get_params(), dtype=np.float64)).to(dev)
+            self.ident_rows = torch.zeros((B, 52), **f64)      # the last identification's result
+            self.ident_cost2 = torch.zeros((B, 2), **f64)
+            self.ident_evals = torch.zeros((B,), **i32)
+            self.ident_status = torch.zeros((B,), **i32)       # KITE_IDENT_* of the last identification
+            self.params_status = torch.zeros((B,), **i32)      # KITE_PARAMS_* of the last set_params_device
+            self._ident_ws = torch.empty((nmpc.ident_workspace_doubles(adapt, B, recorder.T),), **f64)
+            self._ident_ok = nmpc.IDENT_CONVERGED, nmpc.IDENT_NAN
         # a plant of its own (``GpuPlant``, or any object with h, steps and
         # advance): the loop carries the true kite state xp and the time t
         self.plant = plant
@@ -245,6 +287,8 @@ class FleetLoop:
         self.stepper.reset()
         self.x0.copy_(self.x_init)
         self.u0.zero_()
+        if self.adapt is not None:
+            self.recorder.reset()      # a log does not span episodes; the adapted models stay
         if self.plant is not None:
             self.xp.copy_(self.x_init[:, :13])
             self.t = 0.0
@@ -260,6 +304,24 @@ class FleetLoop:
             self.z.copy_(self.x_init[:, 6:13])
             self.ekf_status.zero_()
             self.wind_ekf_fresh = True
+
+    def _adapt(self):
+        """The full log becomes the controller's models, on the stream with no
+        synchronisation: identify from the loop's current rows; a kite whose fit
+        converged to a finite point takes the identified row, any other keeps
+        its row; the rows go to the controller (a row that is no model is
+        rejected there, ``params_status``); the log starts again with the state
+        at hand.  This step's RTI already predicts with the new models."""
+        rec = self.recorder
+        self.stepper.identify(self.adapt, rec.T, self.model_rows, rec.X, rec.U, self.ident_rows, self.ident_cost2,
+                              self.ident_evals, self.ident_status, self._ident_ws)
+        conv, nan = self._ident_ok
+        ok = ((self.ident_status & conv) != 0) & ((self.ident_status & nan) == 0)
+        self.model_rows.copy_(torch.where(ok[:, None], self.ident_rows, self.model_rows))
+        self.stepper.set_params_device(self.model_rows, self.params_status)
+        self.adapt_count += 1
+        rec.reset()
+        rec.record_state(self.x0)
 
     def step(self):
         if self.wind_ekf:
@@ -289,6 +351,8 @@ class FleetLoop:
             self.x0[:, :13].copy_(self.xe)
         if self.recorder is not None:
             self.recorder.record_state(self.x0)
+            if self.adapt is not None and self.recorder.full:
+                self._adapt()
         self.stepper.rti(self.x0, self.u0, self.traj, self.diag, self.status)
         if self.recorder is not None:
             self.recorder.record_control(self.u0)

@@ -27,6 +27,7 @@ PLANT_NAN = 1                      # KITE_PLANT_NAN (plant status word)
 EKF_NAN, EKF_S_NOT_PD = 1, 2       # KITE_EKF_* (status word of the wind-estimating EKF)
 WIND_MAX_DEFAULT = 20.0            # set_wind_device: clamp of an estimated wind component, m/s
 IDENT_NAN, IDENT_CONVERGED, IDENT_AT_BOUND = 1, 2, 4   # KITE_IDENT_* (status word of the identification)
+PARAMS_REJECTED = 1                # KITE_PARAMS_REJECTED (status word of set_params_device)
 IDENT_NP = 21                      # KITE_IDENT_NP
 IDENT_CHUNK = 8                    # KITE_IDENT_CHUNK: samples per partial sum of k_ident_accum
 # the identified parameters in the reference's REF_P order (kite_identification_test.cpp:120-121)
@@ -203,6 +204,9 @@ _SIGNATURES = {
                                                      ctypes.c_void_p]),
     "kite_nmpc_jacobian_wind": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, _DP]),
     "kite_nmpc_set_wind_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]),
+    "kite_nmpc_set_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
+    "kite_nmpc_set_params_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    "kite_nmpc_get_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "kite_ident_default_config": (None, [ctypes.POINTER(IdentConfig)]),
     "kite_ident_param_index": (ctypes.c_int, [ctypes.c_int32]),
     "kite_nmpc_ident_sens": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
@@ -634,6 +638,40 @@ class BatchNMPC:
         ptr, each component clamped to +-wmax, a non-finite one replaced by 0."""
         _check(lib().kite_nmpc_set_wind_device(self._h, ctypes.c_void_p(ptr) if ptr else None, int(stride),
                                                float(wmax)), "set_wind_device")
+
+    # --- per-kite controller models --------------------------------------------
+    def set_params(self, rows=None):
+        """The model of the step's predictions (kite_nmpc_set_params): None =
+        the creation model, one ``KiteParams`` (or 52 values) = one model for
+        every kite, a (B, 52) array = a model per kite (see ``perturb_params``).
+        The item-wise entry points, the EKFs and the plant's default keep the
+        creation model."""
+        if rows is None:
+            _check(lib().kite_nmpc_set_params(self._h, None, 0), "set_params")
+            return
+        if isinstance(rows, KiteParams):
+            rows = rows.as_array()
+        p = _f64(rows)
+        if p.ndim == 1:
+            p = p.reshape(1, -1)
+        if p.ndim != 2 or p.shape[1] != len(_PARAM_FIELDS):
+            raise ValueError("controller parameters: 52 values per kite")
+        _check(lib().kite_nmpc_set_params(self._h, ctypes.c_void_p(p.ctypes.data), p.shape[0]), "set_params")
+
+    def set_params_device(self, ptr: int, count: int, status_ptr: int = 0):
+        """``set_params`` with a row per kite from device memory
+        (kite_nmpc_set_params_device, asynchronous on the context stream): count
+        = B rows of 52 doubles at ptr.  A row that is no model keeps that kite's
+        previous one and sets ``PARAMS_REJECTED`` in the int32 status word at
+        status_ptr (B words, optional)."""
+        v = lambda p: ctypes.c_void_p(p) if p else None
+        _check(lib().kite_nmpc_set_params_device(self._h, v(ptr), int(count), v(status_ptr)), "set_params_device")
+
+    def get_params(self) -> np.ndarray:
+        """The (B, 52) rows in force (kite_nmpc_get_params)."""
+        out = np.zeros((self.batch, len(_PARAM_FIELDS)))
+        _check(lib().kite_nmpc_get_params(self._h, ctypes.c_void_p(out.ctypes.data)), "get_params")
+        return out
 
     def predict(self, x15, u4, tf: float, steps: int = 1):
         x = _f64(x15).reshape(-1, 15); u = _f64(u4).reshape(-1, 4)
