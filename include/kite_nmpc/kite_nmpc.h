@@ -55,7 +55,9 @@ extern "C" {
                                       _ident_normal, _ident_sens, KITE_IDENT_*) and
                                       the per-kite controller models
                                       (kite_nmpc_set_params[_device], _get_params,
-                                      KITE_PARAMS_REJECTED)                       */
+                                      KITE_PARAMS_REJECTED) and the estimators' model
+                                      (kite_nmpc_set/get_estimator_model,
+                                      KITE_EST_MODEL_*)                           */
 #define KITE_PATH_MAX_HARMONICS 8 /* Fourier path: harmonics per axis              */
 
 /* ---- error codes ------------------------------------------------------ */
@@ -419,9 +421,10 @@ int kite_nmpc_set_wind_device(kite_nmpc_ctx* ctx, const double* d_wind, int32_t 
  * kite_nmpc_step[_device] -- cold-start simulation, delay compensation,
  * sensitivities, defects -- with and without a controller wind, at every
  * horizon and with every qp_kernel.  The item-wise entry points (dynamics,
- * jacobian, predict, rk4_sens, colloc_eval, ident_*), both EKFs and the
- * plant's default keep the creation model.  Rows equal to the creation row
- * give the creation model's outputs bit for bit.
+ * jacobian, predict, rk4_sens, colloc_eval, ident_*) and the plant's default
+ * keep the creation model; so do both EKFs unless
+ * kite_nmpc_set_estimator_model (below) hands them the controller's.  Rows
+ * equal to the creation row give the creation model's outputs bit for bit.
  * A row must be a model (kite_nmpc_plant_set_params' rule: every field finite,
  * mass > 0, an invertible inertia, finite derived constants): one bad row is
  * KITE_EINVAL and the previous setting stays whole.  Any other count:
@@ -447,6 +450,25 @@ int kite_nmpc_set_params_device(kite_nmpc_ctx* ctx, const double* d_params52, in
  * left, the creation row B times when none was called.  Waits for the context
  * stream when a per-kite setting is in force.                                 */
 int kite_nmpc_get_params(kite_nmpc_ctx* ctx, kite_params* out);
+/* The model of the two estimators (kite_nmpc_ekf_step[_device],
+ * kite_nmpc_windekf_step[_device]).  KITE_EST_MODEL_CREATION: the creation
+ * model whatever the controller's setting, as every context starts.
+ * KITE_EST_MODEL_CONTROLLER: the controller's models in force at the call --
+ *   the creation model (no kite_nmpc_set_params, or NULL): as with mode 0;
+ *   one model (the count == 1 form): that model, for any `count`;
+ *   a model per kite: kite b of the call filters with the row in force of
+ *     kite b, so `count` must be the context's B (anything else: KITE_EINVAL,
+ *     nothing is launched, x and P stay); a kite whose row the device setter
+ *     rejected filters with the row it kept.
+ * Ordering is the stream's: a filter call issued after
+ * kite_nmpc_set_params_device sees the new rows without synchronisation.
+ * Rows equal to the creation row give the creation model's estimates bit for
+ * bit.  The item-wise entry points (kite_nmpc_jacobian_wind among them) keep
+ * the creation model.  Any other mode: KITE_EINVAL.                          */
+#define KITE_EST_MODEL_CREATION   0
+#define KITE_EST_MODEL_CONTROLLER 1
+int kite_nmpc_set_estimator_model(kite_nmpc_ctx* ctx, int32_t mode);
+int kite_nmpc_get_estimator_model(kite_nmpc_ctx* ctx, int32_t* mode);
 
 /* ---- aerodynamic parameter identification (additive, no version change) ----
  * src/kite_control/kite_identification_test.cpp: fit the 21 aerodynamic

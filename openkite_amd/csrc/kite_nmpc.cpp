@@ -78,6 +78,7 @@ struct kite_nmpc_ctx {
     kite_params model_params1;     // mode 1: its row (kite_nmpc_get_params)
     double* model_tab = nullptr;   // mode 2: [B][kModelTableStride] constants per kite, allocated once
     double* model_rows = nullptr;  // mode 2: B x 52, the kite_params rows in force, allocated once
+    int est_model = KITE_EST_MODEL_CREATION;   // the EKFs' model (kite_nmpc_set_estimator_model)
     // plant simulator (plant_kernels.hip; kite_nmpc_plant_*)
     int plant_count = 0;           // 0: the controller's own model (mc); 1: plant_mc1 for all; B: plant_mc
     ModelConst plant_mc1;          // count == 1
@@ -1143,18 +1144,55 @@ void kite_ekf_default_covariances(double* W169, double* V49, double* P0_169) {
     }
 }
 
+extern "C++" {
+namespace {
+// The model an EKF call filters with (kite_nmpc_set_estimator_model): *mc the
+// model passed by value, *mct the controller's table or nullptr.  With the
+// table in force kite b takes row b, so count must be the context's B.
+int estimator_model(const kite_nmpc_ctx* ctx, int32_t count, const ModelConst** mc, const double** mct) {
+    *mc = &ctx->mc;
+    *mct = nullptr;
+    if (ctx->est_model != KITE_EST_MODEL_CONTROLLER) return KITE_OK;
+    if (ctx->model_mode == 1) *mc = &ctx->model_mc1;
+    if (ctx->model_mode == 2) {
+        if (count != ctx->B) return KITE_EINVAL;
+        *mct = ctx->model_tab;
+    }
+    return KITE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int kite_nmpc_set_estimator_model(kite_nmpc_ctx* ctx, int32_t mode) {
+    if (!ctx || (mode != KITE_EST_MODEL_CREATION && mode != KITE_EST_MODEL_CONTROLLER)) return KITE_EINVAL;
+    ctx->est_model = mode;       // read at each EKF call: no kernel of the captured step depends on it
+    return KITE_OK;
+}
+
+int kite_nmpc_get_estimator_model(kite_nmpc_ctx* ctx, int32_t* mode) {
+    if (!ctx || !mode) return KITE_EINVAL;
+    *mode = ctx->est_model;
+    return KITE_OK;
+}
+
 int kite_nmpc_ekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, double* d_x13, const double* d_u3,
                               double* d_P169, const double* d_z7, const double* d_W169, const double* d_V49) {
     if (!ctx || count < 1 || !d_x13 || !d_u3 || !d_P169 || !d_W169 || (d_z7 && !d_V49) || !std::isfinite(dt))
         return KITE_EINVAL;
+    const ModelConst* mc;
+    const double* mct;
+    { const int rc = estimator_model(ctx, count, &mc, &mct); if (rc) return rc; }
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(kite::launch_ekf(ctx->mc, count, dt, d_x13, d_u3, d_P169, d_z7, d_W169, d_V49, ctx->stream));
+    HIP_TRY(kite::launch_ekf(*mc, mct, count, dt, d_x13, d_u3, d_P169, d_z7, d_W169, d_V49, ctx->stream));
     return KITE_OK;
 }
 
 int kite_nmpc_ekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, double* x13, const double* u3, double* P169,
                        const double* z7, const double* W169, const double* V49) {
     if (!ctx || count < 1 || !x13 || !u3 || !P169 || !W169 || (z7 && !V49) || !std::isfinite(dt)) return KITE_EINVAL;
+    const ModelConst* mc;
+    const double* mct;
+    { const int rc = estimator_model(ctx, count, &mc, &mct); if (rc) return rc; }
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t c = count;
     const size_t nx = c * 13, nu = c * 3, np = c * 169, nz = z7 ? c * 7 : 0;
@@ -1168,7 +1206,7 @@ int kite_nmpc_ekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, double* x13
     if (z7) HIP_TRY(hipMemcpyAsync(dz, z7, nz * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(dW, W169, 169 * sizeof(double), hipMemcpyHostToDevice, s));
     if (V49) HIP_TRY(hipMemcpyAsync(dV, V49, 49 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(kite::launch_ekf(ctx->mc, count, dt, dx, du, dP, z7 ? dz : nullptr, dW, dV, s));
+    HIP_TRY(kite::launch_ekf(*mc, mct, count, dt, dx, du, dP, z7 ? dz : nullptr, dW, dV, s));
     HIP_TRY(hipMemcpyAsync(x13, dx, nx * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(P169, dP, np * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1212,8 +1250,11 @@ int kite_nmpc_windekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, 
     if (!ctx || !d_x16 || !d_u3 || !d_P256 || !d_W256 || (d_z7 && !d_V49)) return KITE_EINVAL;
     const int rc = windekf_args_ok(count, dt, substeps);
     if (rc) return rc;
+    const ModelConst* mc;
+    const double* mct;
+    { const int rcm = estimator_model(ctx, count, &mc, &mct); if (rcm) return rcm; }
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(kite::launch_ekf_wind(ctx->mc, count, dt, substeps, d_x16, d_u3, d_P256, d_z7, d_W256, d_V49, d_status,
+    HIP_TRY(kite::launch_ekf_wind(*mc, mct, count, dt, substeps, d_x16, d_u3, d_P256, d_z7, d_W256, d_V49, d_status,
                                   ctx->stream));
     return KITE_OK;
 }
@@ -1224,6 +1265,9 @@ int kite_nmpc_windekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t
     if (!ctx || !x16 || !u3 || !P256 || !W256 || (z7 && !V49)) return KITE_EINVAL;
     const int rc0 = windekf_args_ok(count, dt, substeps);
     if (rc0) return rc0;
+    const ModelConst* mc;
+    const double* mct;
+    { const int rcm = estimator_model(ctx, count, &mc, &mct); if (rcm) return rcm; }
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t c = count;
     const size_t nx = c * 16, nu = c * 3, np = c * 256, nz = z7 ? c * 7 : 0, ns = (c + 1) / 2;
@@ -1238,7 +1282,7 @@ int kite_nmpc_windekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t
     if (z7) HIP_TRY(hipMemcpyAsync(dz, z7, nz * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(dW, W256, 256 * sizeof(double), hipMemcpyHostToDevice, s));
     if (V49) HIP_TRY(hipMemcpyAsync(dV, V49, 49 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(kite::launch_ekf_wind(ctx->mc, count, dt, substeps, dx, du, dP, z7 ? dz : nullptr, dW, dV, dst, s));
+    HIP_TRY(kite::launch_ekf_wind(*mc, mct, count, dt, substeps, dx, du, dP, z7 ? dz : nullptr, dW, dV, dst, s));
     HIP_TRY(hipMemcpyAsync(x16, dx, nx * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(P256, dP, np * sizeof(double), hipMemcpyDeviceToHost, s));
     if (status) HIP_TRY(hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s));

@@ -263,14 +263,7 @@ __global__ __launch_bounds__(64) void k_prologue_cold(ModelConst P, RtiConst C, 
 // (k_plant's store is field-major because there a LANE is a kite.)
 constexpr int MCT_STRIDE = kModelTableStride;
 static_assert(kModelConstDoubles < MCT_STRIDE, "a table row holds a ModelConst and a pad");
-__device__ __forceinline__ ModelConst model_row(const double* __restrict__ mct, int b) {
-    const double* r = mct + (size_t)b * MCT_STRIDE;
-    ModelConst P;
-    double* g = reinterpret_cast<double*>(&P);
-#pragma unroll
-    for (int i = 0; i < kModelConstDoubles; ++i) g[i] = r[i];
-    return P;
-}
+// (model_row: rti_kernels.hpp, shared with the per-kite EKF)
 
 // k_prologue and k_prologue_cold with a model per kite: the kite's table row
 // instead of the kernel argument (the wave is one kite: a wave-uniform row).

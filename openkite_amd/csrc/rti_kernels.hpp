@@ -85,6 +85,18 @@ hipError_t launch_prologue(const ModelConst& P, const RtiConst& C, int B, int wa
 hipError_t launch_rk4_sens(const ModelConst& P, const RtiConst& C, int B, const double* X, const double* U,
                            double* AB, double* DEF, const double* wind, const double* mct, hipStream_t s);
 constexpr int kModelTableStride = 48;
+// Kite b's table row as a ModelConst, for kernels in which b is wave-uniform
+// (a wave is one kite): the row address is uniform and the row arrives by
+// scalar loads into the SGPRs that hold the kernel-argument ModelConst of the
+// homogeneous kernels.
+__device__ __forceinline__ ModelConst model_row(const double* __restrict__ mct, int b) {
+    const double* r = mct + (size_t)b * kModelTableStride;
+    ModelConst P;
+    double* g = reinterpret_cast<double*>(&P);
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(ModelConst) / sizeof(double)); ++i) g[i] = r[i];
+    return P;
+}
 // every row of the table mct and of the rows in force (rows, B x 52) from one
 // model: its constants P and its kite_params row52 (host pointer)
 hipError_t launch_model_fill(const ModelConst& P, const double* row52, int B, double* mct, double* rows,
@@ -156,15 +168,17 @@ struct CollocConst {
 hipError_t launch_colloc(const ModelConst& P, const CollocConst& C, int count, const double* tab, const double* z,
                          double* G, double* J, double* jac, hipStream_t s);
 // batched EKF propagate (+ update when z != nullptr), in place on x and Pc (ekf_kernels.hip)
-hipError_t launch_ekf(const ModelConst& P, int count, double dt, double* x, const double* u, double* Pc,
-                      const double* z, const double* W, const double* V, hipStream_t s);
+// mct: per-kite model constants, the controller's table ([count][kModelTableStride],
+// kite b filters with row b), or nullptr: every kite takes P (kernel argument)
+hipError_t launch_ekf(const ModelConst& P, const double* mct, int count, double dt, double* x, const double* u,
+                      double* Pc, const double* z, const double* W, const double* V, hipStream_t s);
 // Wind-estimating EKF (windekf_kernels.hip): `substeps` propagations of
 // dt / substeps (+ one update when z != nullptr), in place on x16 (count x 16,
 // [x13 | W3]) and Pc (count x 16 x 16); status: count words (nullable),
-// KITE_EKF_* per kite, written on every call
-hipError_t launch_ekf_wind(const ModelConst& P, int count, double dt, int substeps, double* x16, const double* u,
-                           double* Pc, const double* z, const double* W, const double* V, int32_t* status,
-                           hipStream_t s);
+// KITE_EKF_* per kite, written on every call; mct as launch_ekf's
+hipError_t launch_ekf_wind(const ModelConst& P, const double* mct, int count, double dt, int substeps, double* x16,
+                           const double* u, double* Pc, const double* z, const double* W, const double* V,
+                           int32_t* status, hipStream_t s);
 // J (count x 13 x 16) = [df/dx | df/dW] under the winds w (count x 3)
 hipError_t launch_jacobian_wind(const ModelConst& P, int count, const double* x, const double* u, const double* w,
                                 double* J, hipStream_t s);

@@ -40,6 +40,7 @@
 namespace kite {
 
 constexpr int WEKF_T = 64;            // threads per block = 4 kites x 16 lanes
+constexpr int WEKF_PK_T = 16;         // k_ekf_wind_pk: one kite per block
 constexpr int WEKF_N = 16;            // filter states
 constexpr int WEKF_LD = 17;           // LDS row stride of a 16 x 16 matrix
 constexpr int WEKF_KS = 16 * 17 + 4;  // LDS kite stride
@@ -66,167 +67,43 @@ __global__ __launch_bounds__(WEKF_T) void k_ekf_wind(ModelConst P, int count, do
                                                      double* __restrict__ Pc, const double* __restrict__ z,
                                                      const double* __restrict__ W, const double* __restrict__ V,
                                                      int32_t* __restrict__ status) {
-    __shared__ double sA[4 * WEKF_KS];
-    __shared__ double sN[4 * WEKF_KS];
     const int kk = threadIdx.x >> 4, j = threadIdx.x & 15;
     const int b = blockIdx.x * 4 + kk;
     const bool kite = b < count;
-    double* sa = sA + kk * WEKF_KS;
-    double* sn = sN + kk * WEKF_KS;
-    const double h = dt / (double)substeps;
-
-    // xv: [x13 | W3], every lane of the kite holds all of it; pcol: column j of P
-    double xv[WEKF_N], uv[NKU], pcol[WEKF_N], wcol[WEKF_N];
-    for (int i = 0; i < WEKF_N; ++i) xv[i] = kite ? x[(size_t)b * WEKF_N + i] : 0.0;
-    for (int i = 0; i < NKU; ++i) uv[i] = kite ? u[(size_t)b * NKU + i] : 0.0;
-    for (int i = 0; i < WEKF_N; ++i) pcol[i] = kite ? Pc[((size_t)b * WEKF_N + i) * WEKF_N + j] : 0.0;
-    for (int i = 0; i < WEKF_N; ++i) wcol[i] = W[i * WEKF_N + j];
-
-    bool fin = true;
-    for (int i = 0; i < WEKF_N; ++i) fin = fin && isfinite(xv[i]) && isfinite(pcol[i]);
-    bool alive = !kite_any(!fin, kk);         // uniform over the kite's lanes
-    const bool entry_ok = alive;
-    int32_t flag = alive ? 0 : KITE_EKF_NAN;
-
-#pragma unroll 1
-    for (int s = 0; s < substeps; ++s) {
-        // column j of A = I + J h at the estimate; rows 13..15: W_dot = 0
-        {
-            double jc[NK];
-            wind_jac_col(P, xv, uv, xv + NK, j, jc);
-            for (int i = 0; i < NK; ++i) sa[i * WEKF_LD + j] = jc[i] * h + (i == j ? 1.0 : 0.0);
-            for (int i = NK; i < WEKF_N; ++i) sa[i * WEKF_LD + j] = (i == j ? 1.0 : 0.0);
-        }
-        // x13+ = one RK4 step over h under the estimated wind (every lane of the kite)
-        double xn[NK];
-        {
-            double k[NK], xs[NK];
-            for (int i = 0; i < NK; ++i) { xn[i] = xv[i]; xs[i] = xv[i]; }
-#pragma unroll 1
-            for (int st = 0; st < 4; ++st) {
-                kite_rhs<double, true>(P, xs, uv, k, xv + NK);
-                const double wa = (st == 0 || st == 3) ? h / 6.0 : h / 3.0;
-                const double wn = (st < 2) ? 0.5 * h : h;
-                for (int i = 0; i < NK; ++i) { xn[i] += wa * k[i]; xs[i] = xv[i] + wn * k[i]; }
-            }
-        }
-        __syncthreads();
-        // (A P)[:, j]
-        for (int i = 0; i < WEKF_N; ++i) {
-            double t = 0.0;
-            for (int k = 0; k < WEKF_N; ++k) t = fma(sa[i * WEKF_LD + k], pcol[k], t);
-            sn[i * WEKF_LD + j] = t;
-        }
-        __syncthreads();
-        // P+[:, j] = sum_k (A P)[:, k] A[j][k] + Wcov[:, j]
-        double pn[WEKF_N];
-        for (int i = 0; i < WEKF_N; ++i) {
-            double t = wcol[i];
-            for (int k = 0; k < WEKF_N; ++k) t = fma(sn[i * WEKF_LD + k], sa[j * WEKF_LD + k], t);
-            pn[i] = t;
-        }
-        bool ok = true;
-        for (int i = 0; i < NK; ++i) ok = ok && isfinite(xn[i]);
-        for (int i = 0; i < WEKF_N; ++i) ok = ok && isfinite(pn[i]);
-        const bool bad = kite_any(!ok, kk);
-        if (alive && bad) { alive = false; flag = KITE_EKF_NAN; }   // keeps the last finite x16, P
-        if (alive) {
-            for (int i = 0; i < NK; ++i) xv[i] = xn[i];
-            for (int i = 0; i < WEKF_N; ++i) pcol[i] = pn[i];
-        }
-        __syncthreads();                     // sa, sn are rewritten by the next substep
-    }
-
-    if (z) {                                 // uniform over the grid
-        for (int i = 0; i < WEKF_N; ++i) sn[i * WEKF_LD + j] = pcol[i];
-        __syncthreads();
-        // S = P+[6:13, 6:13] + V, Cholesky in registers (lower), every lane its own copy
-        double L[7][7];
-        for (int a = 0; a < 7; ++a)
-            for (int c = 0; c <= a; ++c) L[a][c] = kite ? sn[(6 + a) * WEKF_LD + 6 + c] + V[a * 7 + c] : (a == c);
-        bool pd = true;
-        for (int c = 0; c < 7; ++c) {
-            double d = L[c][c];
-            for (int k = 0; k < c; ++k) d -= L[c][k] * L[c][k];
-            pd = pd && (d > 0.0) && isfinite(d);
-            d = sqrt(d);
-            L[c][c] = d;
-            for (int a = c + 1; a < 7; ++a) {
-                double t = L[a][c];
-                for (int k = 0; k < c; ++k) t -= L[a][k] * L[c][k];
-                L[a][c] = t / d;
-            }
-        }
-        auto solve = [&](double r[7]) {          // r <- S^-1 r
-            for (int a = 0; a < 7; ++a) {
-                double t = r[a];
-                for (int k = 0; k < a; ++k) t -= L[a][k] * r[k];
-                r[a] = t / L[a][a];
-            }
-            for (int a = 6; a >= 0; --a) {
-                double t = r[a];
-                for (int k = a + 1; k < 7; ++k) t -= L[k][a] * r[k];
-                r[a] = t / L[a][a];
-            }
-        };
-        // P[:, j] = P+[:, j] - P+[:, 6:13] S^-1 P+[6:13, j]
-        double pu[WEKF_N], xu[WEKF_N];
-        {
-            double c7[7];
-            for (int a = 0; a < 7; ++a) c7[a] = pcol[6 + a];
-            solve(c7);
-            for (int i = 0; i < WEKF_N; ++i) {
-                double t = pcol[i];
-                for (int a = 0; a < 7; ++a) t = fma(-sn[i * WEKF_LD + 6 + a], c7[a], t);
-                pu[i] = t;
-            }
-        }
-        // x = x+ + P+[:, 6:13] S^-1 (z - x+[6:13])
-        {
-            double y[7];
-            for (int a = 0; a < 7; ++a) y[a] = (kite ? z[(size_t)b * 7 + a] : 0.0) - xv[6 + a];
-            solve(y);
-            for (int i = 0; i < WEKF_N; ++i) {
-                double t = xv[i];
-                for (int a = 0; a < 7; ++a) t = fma(sn[i * WEKF_LD + 6 + a], y[a], t);
-                xu[i] = t;
-            }
-        }
-        bool ok = true;
-        for (int i = 0; i < WEKF_N; ++i) ok = ok && isfinite(pu[i]) && isfinite(xu[i]);
-        const bool bad = kite_any(!ok, kk);
-        if (alive && !pd) flag |= KITE_EKF_S_NOT_PD;            // update skipped
-        else if (alive && bad) flag |= KITE_EKF_NAN;            // keeps the propagated estimate
-        const bool updated = alive && pd && !bad;
-        if (updated) {
-            for (int i = 0; i < WEKF_N; ++i) { pcol[i] = pu[i]; xv[i] = xu[i]; }
-        }
-        // P <- (P + P') / 2 of an updated kite.  S is factored from its lower
-        // triangle alone, so the update does not damp an antisymmetric part of
-        // P: rounding seeds one and every further update multiplies it (by 1.4
-        // to 1.6 per period in the open-loop run of the tests: 1e-15 becomes
-        // 1e-10 within 40 periods and O(1) within 100).  Both halves of a pair
-        // add the same two numbers, so P leaves exactly symmetric.
-        __syncthreads();                     // every lane is done with P+ in sn
-        for (int i = 0; i < WEKF_N; ++i) sn[i * WEKF_LD + j] = pcol[i];
-        __syncthreads();
-        if (updated)
-            for (int i = 0; i < WEKF_N; ++i) pcol[i] = 0.5 * (pcol[i] + sn[j * WEKF_LD + i]);
-    }
-    // a kite that was non-finite on entry is left untouched; one frozen in a
-    // substep stores the last finite x16 and P it holds
-    if (kite && entry_ok)
-        for (int i = 0; i < WEKF_N; ++i) Pc[((size_t)b * WEKF_N + i) * WEKF_N + j] = pcol[i];
-    if (kite && entry_ok && j == 0)
-        for (int i = 0; i < WEKF_N; ++i) x[(size_t)b * WEKF_N + i] = xv[i];
-    if (kite && j == 0 && status) status[b] = flag;
+#include "windekf_body.inc"
 }
 
-hipError_t launch_ekf_wind(const ModelConst& P, int count, double dt, int substeps, double* x16, const double* u,
-                           double* Pc, const double* z, const double* W, const double* V, int32_t* status,
-                           hipStream_t s) {
-    hipLaunchKernelGGL(k_ekf_wind, dim3((count + 3) / 4), dim3(WEKF_T), 0, s, P, count, dt, substeps, x16, u, Pc, z,
-                       W, V, status);
+// k_ekf_wind with a model per kite: kite b filters with row b of the
+// controller's table mct ([count][kModelTableStride], rti_kernels.hpp).  With
+// four kites per wave the 47 constants would be lane-varying: 94 more VGPRs in
+// a kernel that sits at 458 of 512, which spills (30 VGPRs, 124 bytes of
+// scratch), and lane-varying constants change which multiplies and adds the
+// compiler fuses (k_ekf_pk, ekf_kernels.hip).  So here a block is ONE kite: 16 threads, the kite's 16 columns, grid
+// `count`; the row is wave-uniform and arrives by scalar loads (model_row, as
+// in k_prologue_pk), and the kernel has k_ekf_wind's registers and
+// instructions.  kk is 0 and no kite is out of range; the included body keeps
+// its predication and walks the same barriers.
+__global__ __launch_bounds__(WEKF_T) void k_ekf_wind_pk(const double* __restrict__ mct, int count, double dt,
+                                                        int substeps, double* __restrict__ x,
+                                                        const double* __restrict__ u, double* __restrict__ Pc,
+                                                        const double* __restrict__ z, const double* __restrict__ W,
+                                                        const double* __restrict__ V, int32_t* __restrict__ status) {
+    const int kk = threadIdx.x >> 4, j = threadIdx.x & 15;      // kk = 0: 16 threads
+    const int b = blockIdx.x + kk;
+    const bool kite = b < count;
+    const ModelConst P = model_row(mct, blockIdx.x);
+#include "windekf_body.inc"
+}
+
+hipError_t launch_ekf_wind(const ModelConst& P, const double* mct, int count, double dt, int substeps, double* x16,
+                           const double* u, double* Pc, const double* z, const double* W, const double* V,
+                           int32_t* status, hipStream_t s) {
+    if (mct)
+        hipLaunchKernelGGL(k_ekf_wind_pk, dim3(count), dim3(WEKF_PK_T), 0, s, mct, count, dt, substeps, x16, u,
+                           Pc, z, W, V, status);
+    else
+        hipLaunchKernelGGL(k_ekf_wind, dim3((count + 3) / 4), dim3(WEKF_T), 0, s, P, count, dt, substeps, x16, u, Pc,
+                           z, W, V, status);
     return hipGetLastError();
 }
 

@@ -31,7 +31,10 @@ One step of a fleet of kites on one rank:
          flight log is full, before the RTI, every kite's 21 aerodynamic
          coefficients are identified from it (kite_nmpc_identify_device) and
          become that kite's controller model (kite_nmpc_set_params_device),
-         all on the stream.
+         all on the stream.  With ``estimator_model="controller"`` the
+         estimator filters with those models too (kite_nmpc_set_estimator_model),
+         from the step after the identification on; the default keeps the
+         creation model in the filter.
 
 The stepper does the arithmetic; ``GpuStepper`` drives libkite_nmpc.so on
 device tensors.  Tests plug a CPU oracle stepper into the same loop to check
@@ -82,6 +85,10 @@ class GpuStepper:
         KITE_PARAMS_* words."""
         assert rows.dtype == torch.float64 and rows.is_contiguous() and rows.shape[1] == 52
         self.ctx.set_params_device(rows.data_ptr(), rows.shape[0], status.data_ptr() if status is not None else 0)
+
+    def set_estimator_model(self, mode: int):
+        """The model of the stepper's EKFs (``BatchNMPC.set_estimator_model``)."""
+        self.ctx.set_estimator_model(mode)
 
     def get_params(self):
         """The (B, 52) rows in force, on the host."""
@@ -199,9 +206,14 @@ class FleetLoop:
 
     def __init__(self, stepper, x0: torch.Tensor, N: int, dt: float, ekf: bool = False, ekf_substeps: int = 5,
                  covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None,
-                 plant=None, wind_ekf: bool = False, wind_max: float = 20.0, recorder=None, adapt=None):
+                 plant=None, wind_ekf: bool = False, wind_max: float = 20.0, recorder=None, adapt=None,
+                 estimator_model: str = "creation"):
         if ekf and wind_ekf:
             raise ValueError("ekf and wind_ekf are two estimators: choose one")
+        if estimator_model not in ("creation", "controller"):
+            raise ValueError('estimator_model is "creation" or "controller"')
+        if estimator_model == "controller" and not (ekf or wind_ekf):
+            raise ValueError('estimator_model="controller" needs an estimator: ekf=True or wind_ekf=True')
         if adapt is not None and recorder is None:
             raise ValueError("adapt identifies from a flight log: give the loop a recorder")
         B = x0.shape[0]
@@ -248,6 +260,13 @@ class FleetLoop:
             self.z = self.x0[:, 6:13].clone()
             self.ekf_status = torch.zeros((B,), dtype=torch.int32, device=dev)
             self.wind_ekf_fresh = True
+        # the estimator filters with the controller's models in force (per kite
+        # once ``adapt`` or set_params_device has set them) instead of the
+        # creation model; "creation" calls nothing
+        self.estimator_model = estimator_model
+        if estimator_model == "controller":
+            from . import nmpc
+            stepper.set_estimator_model(nmpc.EST_MODEL_CONTROLLER)
         self.gathered = None
         # a ``FlightRecorder``: the state handed to the controller and the control
         # applied, one period per step, until it is full

@@ -28,6 +28,8 @@ EKF_NAN, EKF_S_NOT_PD = 1, 2       # KITE_EKF_* (status word of the wind-estimat
 WIND_MAX_DEFAULT = 20.0            # set_wind_device: clamp of an estimated wind component, m/s
 IDENT_NAN, IDENT_CONVERGED, IDENT_AT_BOUND = 1, 2, 4   # KITE_IDENT_* (status word of the identification)
 PARAMS_REJECTED = 1                # KITE_PARAMS_REJECTED (status word of set_params_device)
+EST_MODEL_CREATION = 0             # KITE_EST_MODEL_*: the model of the two EKFs (set_estimator_model)
+EST_MODEL_CONTROLLER = 1
 IDENT_NP = 21                      # KITE_IDENT_NP
 IDENT_CHUNK = 8                    # KITE_IDENT_CHUNK: samples per partial sum of k_ident_accum
 # the identified parameters in the reference's REF_P order (kite_identification_test.cpp:120-121)
@@ -207,6 +209,8 @@ _SIGNATURES = {
     "kite_nmpc_set_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "kite_nmpc_set_params_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "kite_nmpc_get_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "kite_nmpc_set_estimator_model": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "kite_nmpc_get_estimator_model": (ctypes.c_int, [ctypes.c_void_p, _IP]),
     "kite_ident_default_config": (None, [ctypes.POINTER(IdentConfig)]),
     "kite_ident_param_index": (ctypes.c_int, [ctypes.c_int32]),
     "kite_nmpc_ident_sens": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
@@ -644,8 +648,8 @@ class BatchNMPC:
         """The model of the step's predictions (kite_nmpc_set_params): None =
         the creation model, one ``KiteParams`` (or 52 values) = one model for
         every kite, a (B, 52) array = a model per kite (see ``perturb_params``).
-        The item-wise entry points, the EKFs and the plant's default keep the
-        creation model."""
+        The item-wise entry points and the plant's default keep the creation
+        model; so do the EKFs unless ``set_estimator_model`` says otherwise."""
         if rows is None:
             _check(lib().kite_nmpc_set_params(self._h, None, 0), "set_params")
             return
@@ -672,6 +676,20 @@ class BatchNMPC:
         out = np.zeros((self.batch, len(_PARAM_FIELDS)))
         _check(lib().kite_nmpc_get_params(self._h, ctypes.c_void_p(out.ctypes.data)), "get_params")
         return out
+
+    def set_estimator_model(self, mode: int):
+        """The model of ``ekf_step`` / ``wind_ekf_step`` and their device forms
+        (kite_nmpc_set_estimator_model): ``EST_MODEL_CREATION`` (the default) or
+        ``EST_MODEL_CONTROLLER``, the controller's models in force at each call
+        (``set_params[_device]``).  With a model per kite in force kite b
+        filters with row b and a call's count must be the batch."""
+        _check(lib().kite_nmpc_set_estimator_model(self._h, int(mode)), "set_estimator_model")
+
+    @property
+    def estimator_model(self) -> int:
+        m = ctypes.c_int32(0)
+        _check(lib().kite_nmpc_get_estimator_model(self._h, ctypes.byref(m)), "get_estimator_model")
+        return int(m.value)
 
     def predict(self, x15, u4, tf: float, steps: int = 1):
         x = _f64(x15).reshape(-1, 15); u = _f64(u4).reshape(-1, 4)
