@@ -57,7 +57,9 @@ extern "C" {
                                       (kite_nmpc_set_params[_device], _get_params,
                                       KITE_PARAMS_REJECTED) and the estimators' model
                                       (kite_nmpc_set/get_estimator_model,
-                                      KITE_EST_MODEL_*)                           */
+                                      KITE_EST_MODEL_*) and the identification under
+                                      a logged wind (kite_nmpc_identify_wind[_device],
+                                      _ident_normal_wind, _ident_sens_wind)       */
 #define KITE_PATH_MAX_HARMONICS 8 /* Fourier path: harmonics per axis              */
 
 /* ---- error codes ------------------------------------------------------ */
@@ -480,7 +482,8 @@ int kite_nmpc_get_estimator_model(kite_nmpc_ctx* ctx, int32_t* mode);
  * everything else of a kite's kite_params row is a known constant of that kite.
  * Log per kite: X (T+1) x 13, U T x 3 (T, dE, dR), sample interval h.
  *   model      RK4, `substeps` substeps of h / substeps under the held control,
- *              no wind (the plant's integrator)
+ *              no wind (the plant's integrator); the _wind entries below take a
+ *              logged wind
  *   segments   the log is cut into segments of `segment` = L samples; a segment
  *              starts at the measured X[k0] with zero sensitivity and predicts
  *              x^_{k0+1} .. x^_{k0+L} (the last one may be shorter).  L = 1: the
@@ -558,6 +561,40 @@ int kite_nmpc_identify_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, 
 /* Workspace of the device variant in doubles; KITE_EINVAL (negative) for
  * arguments kite_nmpc_identify refuses.                                       */
 int64_t kite_nmpc_ident_workspace_doubles(const kite_ident_config* cfg, int32_t count, int32_t T);
+/* ---- the identification under a logged wind (additive, no version change) ----
+ * The same fit with a KNOWN world-frame wind per sample [m/s]: the model's
+ * aerodynamics see v_a = v - q^-1 (x) [0,W] (x) q (kite_nmpc_set_wind's
+ * model), gravity, tether and kinematics keep v.  The unknowns stay the 21;
+ * formulation, iteration rule, chunking, slab and workspace
+ * (kite_nmpc_ident_workspace_doubles serves both forms) are those above.
+ * Wind log per kite: W T x 3, row k held over sample interval k exactly as
+ * U[k] is; a constant wind is a log of equal rows.  Where it comes from is the
+ * caller's business: a wind known for a sweep, or the wind EKF's estimate
+ * (kite_nmpc_windekf_step).  The plant's gust (kite_nmpc_plant_set_wind) varies
+ * inside a sample while the log holds one value per sample: a log of a gusting
+ * plant is an approximation, a constant wind is exact.
+ * The argument rules are those of the windless entries.  A NULL wind pointer
+ * runs the windless kernels and is bit for bit the windless entry.  A
+ * non-finite wind entry makes that kite's cost non-finite: the kite returns its
+ * input row with KITE_IDENT_NAN, the others are not affected.
+ * kite_nmpc_ident_sens_wind: w3 count x 3, the item's wind.                    */
+int kite_nmpc_ident_sens_wind(kite_nmpc_ctx* ctx, int32_t count, double h, int32_t substeps,
+                              const kite_params* params, int32_t nparams, const double* x13, const double* u3,
+                              const double* w3, double* x13_out, double* S);
+/* W: count x T x 3. */
+int kite_nmpc_ident_normal_wind(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                                const kite_params* params, int32_t nparams, const double* p21, const double* X,
+                                const double* U, const double* W, double* A, double* g, double* cost,
+                                int32_t* status);
+int kite_nmpc_identify_wind(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                            const kite_params* params, int32_t nparams, const double* X, const double* U,
+                            const double* W, kite_params* params_out, double* cost2, int32_t* evals,
+                            int32_t* status);
+/* d_W: count x T x 3 on the device, read by every one of the 2 * iters launches. */
+int kite_nmpc_identify_wind_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                                   const double* d_params, int32_t nparams, const double* d_X, const double* d_U,
+                                   const double* d_W, double* d_params_out, double* d_cost2, int32_t* d_evals,
+                                   int32_t* d_status, double* d_workspace);
 
 /* Per-kernel device time [ms] of the last step (cfg.timing = 1):
  * [prologue, rk4_sens, condense, qp, total, qp_main]; qp is the whole QP

@@ -23,6 +23,14 @@
 //   clipped trial, status and lambda.  With `normal` it stops after the sum and
 //   writes A, g and the cost (kite_nmpc_ident_normal).
 // k_ident_sens   one sample interval per item: x+ and d x+ / d p (unscaled).
+// k_ident_accum_w, k_ident_sens_w  the same bodies (ident_accum_body.inc,
+//   ident_sens_body.inc) under a known world-frame wind per sample: the
+//   aerodynamics see v_a = v - q^-1 (x) [0,W] (x) q.  Per stage the first term
+//   is kite_rhs<Dual, true> (v_a depends on q, whose tangent the Dual carries),
+//   the second kite_rhs_dp<true> at v_a (v_a does not depend on the 21).  The
+//   sample's wind is three doubles per lane, loaded where the control is.  The
+//   windless kernels include the same bodies with WIND = false and are, as
+//   compiled, what they were before the wind instances existed.
 //
 // Barriers: the items of a block share every barrier.  No lane returns or
 // leaves a loop early, all trip counts are kernel arguments; an out-of-range
@@ -45,8 +53,12 @@ constexpr int ID_LD = NP + 1;         // LDS row stride of a 13 x 21 sensitivity
 // the sample interval under the held control for direction j: x (value and
 // tangent column j, scaled by sc) advanced by `substeps` RK4 substeps of hs.
 // The value part repeats plant_lane's (plant_kernels.hip) stage arithmetic.
+// WIND: the sample's world-frame wind wnd[0..2], plain doubles held over the
+// interval as u is; WIND = false is the windless interval, instruction for
+// instruction.
+template <bool WIND>
 __device__ __forceinline__ void ident_interval(const ModelConst& P, Dual* x, const double* u, double hs, int substeps,
-                                               int j, double sc) {
+                                               int j, double sc, const double* wnd = nullptr) {
     Dual ud[NKU];
 #pragma unroll
     for (int i = 0; i < NKU; ++i) ud[i] = mk(u[i], 0.0);
@@ -60,11 +72,21 @@ __device__ __forceinline__ void ident_interval(const ModelConst& P, Dual* x, con
             // the model constants are read from LDS in every stage: hoisted out of
             // the loops they would hold 94 registers next to the RK4 state
             asm volatile("" ::: "memory");
-            kite_rhs<Dual>(P, xs, ud, kv);
-            double xv[6], fp[6];
+            double fp[6];
+            if constexpr (WIND) {
+                // v_a depends on q, whose tangent the Dual carries; d f / d p_j at v_a
+                kite_rhs<Dual, true>(P, xs, ud, kv, wnd);
+                double xv[NK];
 #pragma unroll
-            for (int i = 0; i < 6; ++i) xv[i] = xs[i].v;
-            kite_rhs_dp(P, xv, u, j, sc, fp);
+                for (int i = 0; i < NK; ++i) xv[i] = xs[i].v;
+                kite_rhs_dp<true>(P, xv, u, j, sc, fp, wnd);
+            } else {
+                kite_rhs<Dual>(P, xs, ud, kv);
+                double xv[6];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) xv[i] = xs[i].v;
+                kite_rhs_dp(P, xv, u, j, sc, fp);
+            }
 #pragma unroll
             for (int i = 0; i < 6; ++i) kv[i].t += fp[i];
             const double wa = (st == 0 || st == 3) ? hs / 6.0 : hs / 3.0;
@@ -107,76 +129,18 @@ __global__ __launch_bounds__(ID_T) void k_ident_accum(IdentConst C, const double
                                                       const double* __restrict__ state,
                                                       const double* __restrict__ X, const double* __restrict__ U,
                                                       double* __restrict__ slab) {
-    __shared__ ModelConst sP[ID_ITEMS + 1];
-    __shared__ double sS[(ID_ITEMS + 1) * NK * ID_LD];
-    const IdLane l = id_lane();
-    const long long item = (long long)blockIdx.x * ID_ITEMS + l.it;
-    const int kite = (int)(item / C.nchunks), chunk = (int)(item - (long long)kite * C.nchunks);
-    bool valid = l.on && kite < C.count;
-    // a kite that is finished (converged, or its row is no model) does no further work
-    if (valid && state) valid = ((int)state[(size_t)kite * ID_STATE + ID_S_FLAGS] & (ID_F_DONE | ID_F_DEAD)) == 0;
-    const double* row = rows + (size_t)(C.nparams == 1 ? 0 : (valid ? kite : 0)) * 52;
-    const double sc = id_setup(sP, l, valid, row, p21 ? p21 + (size_t)(valid ? kite : 0) * p_stride : nullptr);
-    __syncthreads();
-    const ModelConst& P = sP[l.it];
-    double* sm = sS + l.it * NK * ID_LD;
-    const double* Xk = X + (size_t)(valid ? kite : 0) * (C.T + 1) * NK;
-    const double* Uk = U + (size_t)(valid ? kite : 0) * C.T * NKU;
+    constexpr bool WIND = false;
+    const double* const W = nullptr;          // no wind log: the body's WIND branches are dead
+#include "ident_accum_body.inc"
+}
 
-    double aA[NP], ag = 0.0, ac = 0.0;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) aA[i] = 0.0;
-
-    if (__any(valid)) {                      // uniform over the block (one wavefront)
-#pragma unroll 1
-        for (int sg = 0; sg < C.spc; ++sg) {
-            const long long k0 = ((long long)chunk * C.spc + sg) * C.L;
-            const bool sv = valid && k0 < C.T;
-            Dual x[NK];
-#pragma unroll
-            for (int i = 0; i < NK; ++i) x[i] = mk(sv ? Xk[(size_t)k0 * NK + i] : 0.0, 0.0);
-#pragma unroll 1
-            for (int a = 0; a < C.L; ++a) {
-                const long long k = k0 + a;
-                const bool on = sv && k < C.T;
-                double u[NKU];
-#pragma unroll
-                for (int i = 0; i < NKU; ++i) u[i] = on ? Uk[(size_t)k * NKU + i] : 0.0;
-                ident_interval(P, x, u, C.hs, C.substeps, l.j, sc);
-                // column j of S~ and (lane 0) the residual e into LDS: row r holds
-                // S~[r][0..20] and e_r
-#pragma unroll
-                for (int r = 0; r < NK; ++r) sm[r * ID_LD + l.j] = x[r].t;
-                if (l.j == 0)
-#pragma unroll
-                    for (int r = 0; r < NK; ++r) sm[r * ID_LD + NP] = on ? Xk[(size_t)(k + 1) * NK + r] - x[r].v : 0.0;
-                __syncthreads();
-                if (on) {
-#pragma unroll 1
-                    for (int r = 0; r < NK; ++r) {
-                        const double* sr = sm + r * ID_LD;
-                        const double e = sr[NP], q = C.Q[r];
-                        const double qe = q * e;
-                        const double t = q * sr[l.j];
-                        ac = fma(qe, e, ac);
-                        ag = fma(sr[l.j], qe, ag);
-#pragma unroll
-                        for (int i = 0; i < NP; ++i) aA[i] = fma(sr[i], t, aA[i]);
-                    }
-                }
-                __syncthreads();             // sm is rewritten by the next sample
-            }
-        }
-    }
-    if (valid) {
-        double* out = slab + ((size_t)kite * C.nchunks + chunk) * ID_SLAB;
-        const int base = l.j * (l.j + 1) / 2;            // A[i][j], i <= j, packed by columns
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-            if (i <= l.j) out[base + i] = aA[i];
-        out[ID_SLAB_G + l.j] = ag;
-        if (l.j == 0) out[ID_SLAB_C] = ac;
-    }
+__global__ __launch_bounds__(ID_T) void k_ident_accum_w(IdentConst C, const double* __restrict__ rows,
+                                                        const double* __restrict__ p21, int p_stride,
+                                                        const double* __restrict__ state,
+                                                        const double* __restrict__ X, const double* __restrict__ U,
+                                                        const double* __restrict__ W, double* __restrict__ slab) {
+    constexpr bool WIND = true;
+#include "ident_accum_body.inc"
 }
 
 __device__ __forceinline__ int id_packed(int i, int j) {      // index of A[i][j] in the packed upper triangle
@@ -370,35 +334,29 @@ __global__ __launch_bounds__(ID_T) void k_ident_sens(int count, int nparams, dou
                                                      const double* __restrict__ rows,
                                                      const double* __restrict__ x13, const double* __restrict__ u3,
                                                      double* __restrict__ xo, double* __restrict__ S) {
-    __shared__ ModelConst sP[ID_ITEMS + 1];
-    const IdLane l = id_lane();
-    const long long item = (long long)blockIdx.x * ID_ITEMS + l.it;
-    const bool valid = l.on && item < count;
-    const size_t b = valid ? (size_t)item : 0;
-    const double* row = rows + (nparams == 1 ? 0 : b) * 52;
-    id_setup(sP, l, valid, row, nullptr);
-    __syncthreads();
-    Dual x[NK];
-    double u[NKU];
-#pragma unroll
-    for (int i = 0; i < NK; ++i) x[i] = mk(valid ? x13[b * NK + i] : 0.0, 0.0);
-#pragma unroll
-    for (int i = 0; i < NKU; ++i) u[i] = valid ? u3[b * NKU + i] : 0.0;
-    ident_interval(sP[l.it], x, u, hs, substeps, l.j, 1.0);
-    if (valid) {
-#pragma unroll
-        for (int r = 0; r < NK; ++r) S[(b * NK + r) * NP + l.j] = x[r].t;
-        if (l.j == 0)
-#pragma unroll
-            for (int r = 0; r < NK; ++r) xo[b * NK + r] = x[r].v;
-    }
+    constexpr bool WIND = false;
+    const double* const w3 = nullptr;
+#include "ident_sens_body.inc"
+}
+
+__global__ __launch_bounds__(ID_T) void k_ident_sens_w(int count, int nparams, double hs, int substeps,
+                                                       const double* __restrict__ rows,
+                                                       const double* __restrict__ x13, const double* __restrict__ u3,
+                                                       const double* __restrict__ w3,
+                                                       double* __restrict__ xo, double* __restrict__ S) {
+    constexpr bool WIND = true;
+#include "ident_sens_body.inc"
 }
 
 hipError_t launch_ident_accum(const IdentConst& C, const double* rows, const double* p21, int p_stride,
-                              const double* state, const double* X, const double* U, double* slab, hipStream_t s) {
+                              const double* state, const double* X, const double* U, const double* W, double* slab,
+                              hipStream_t s) {
     const long long items = (long long)C.count * C.nchunks;
-    hipLaunchKernelGGL(k_ident_accum, dim3((unsigned)((items + ID_ITEMS - 1) / ID_ITEMS)), dim3(ID_T), 0, s, C, rows,
-                       p21, p_stride, state, X, U, slab);
+    const dim3 grid((unsigned)((items + ID_ITEMS - 1) / ID_ITEMS));
+    if (W)
+        hipLaunchKernelGGL(k_ident_accum_w, grid, dim3(ID_T), 0, s, C, rows, p21, p_stride, state, X, U, W, slab);
+    else
+        hipLaunchKernelGGL(k_ident_accum, grid, dim3(ID_T), 0, s, C, rows, p21, p_stride, state, X, U, slab);
     return hipGetLastError();
 }
 
@@ -411,9 +369,13 @@ hipError_t launch_ident_solve(const IdentConst& C, int first, int normal, const 
 }
 
 hipError_t launch_ident_sens(int count, int nparams, double hs, int substeps, const double* rows, const double* x13,
-                             const double* u3, double* xo, double* S, hipStream_t s) {
-    hipLaunchKernelGGL(k_ident_sens, dim3((count + ID_ITEMS - 1) / ID_ITEMS), dim3(ID_T), 0, s, count, nparams, hs,
-                       substeps, rows, x13, u3, xo, S);
+                             const double* u3, const double* w3, double* xo, double* S, hipStream_t s) {
+    const dim3 grid((count + ID_ITEMS - 1) / ID_ITEMS);
+    if (w3)
+        hipLaunchKernelGGL(k_ident_sens_w, grid, dim3(ID_T), 0, s, count, nparams, hs, substeps, rows, x13, u3, w3, xo,
+                           S);
+    else
+        hipLaunchKernelGGL(k_ident_sens, grid, dim3(ID_T), 0, s, count, nparams, hs, substeps, rows, x13, u3, xo, S);
     return hipGetLastError();
 }
 

@@ -34,15 +34,18 @@ constexpr int ID_F_DEAD = 4;    // the row is no model
 
 // rows: nparams x 52 (kite_params); p21: parameter values of the evaluation,
 // kite b's at p21 + b p_stride, or nullptr (the rows' own); state: nullptr or
-// the iteration state (finished kites are skipped); slab: count x nchunks x ID_SLAB
+// the iteration state (finished kites are skipped); slab: count x nchunks x ID_SLAB;
+// W: the wind log count x T x 3 (k_ident_accum_w), or nullptr (k_ident_accum)
 hipError_t launch_ident_accum(const IdentConst& C, const double* rows, const double* p21, int p_stride,
-                              const double* state, const double* X, const double* U, double* slab, hipStream_t s);
+                              const double* state, const double* X, const double* U, const double* W, double* slab,
+                              hipStream_t s);
 // normal: A (count x 21 x 21), g, cost, status at p21 (count x 21) from the slab;
 // otherwise one iteration on `state` (first: initialise it), and the outputs
 hipError_t launch_ident_solve(const IdentConst& C, int first, int normal, const double* rows, const double* p21,
                               const double* slab, double* state, double* A, double* g, double* cost,
                               double* params_out, double* cost2, int32_t* evals, int32_t* status, hipStream_t s);
+// w3: the items' wind count x 3 (k_ident_sens_w), or nullptr (k_ident_sens)
 hipError_t launch_ident_sens(int count, int nparams, double hs, int substeps, const double* rows, const double* x13,
-                             const double* u3, double* xo, double* S, hipStream_t s);
+                             const double* u3, const double* w3, double* xo, double* S, hipStream_t s);
 
 }  // namespace kite

@@ -64,11 +64,29 @@ __host__ __device__ __forceinline__ ModelConst ident_model_const(const double* r
     return m;
 }
 
-// fp[0..5] = sc * d f[0..5] / d p_j at (x, u); d f[6..12] / d p_j = 0
+// fp[0..5] = sc * d f[0..5] / d p_j at (x, u); d f[6..12] / d p_j = 0.
+// WIND (kite_rhs<T, true>): the 21 enter only the aerodynamic forces and
+// moments, which see the air-relative body velocity v_a = v - q^-1 (x) [0,W] (x) q,
+// and v_a does not depend on them: the columns are the same scalars times the
+// same directions with v_a in place of v (the rates w are the kite's own).  x
+// then holds all 13 states (q = x[9..12]) and wnd the world-frame wind; v_a is
+// written as the value part of kite_rhs<Dual, true> writes it.
+template <bool WIND = false>
 __device__ __forceinline__ void kite_rhs_dp(const ModelConst& P, const double* x, const double* u, int j, double sc,
-                                            double* fp) {
-    const double vx = x[0], vy = x[1], vz = x[2];
+                                            double* fp, const double* wnd = nullptr) {
+    double vx = x[0], vy = x[1], vz = x[2];
     const double wx = x[3], wy = x[4], wz = x[5];
+    if constexpr (WIND) {
+        const double qw = x[9], qx = x[10], qy = x[11], qz = x[12];
+        const double wwuu = qw * qw - (qx * qx + qy * qy + qz * qz);
+        const double W0 = wnd[0], W1 = wnd[1], W2 = wnd[2];
+        const double uv2 = 2.0 * (qx * W0 + qy * W1 + qz * W2);
+        const double cx = qy * W2 - qz * W1, cy = qz * W0 - qx * W2, cz = qx * W1 - qy * W0;
+        const double w2 = 2.0 * qw;
+        vx = vx - (wwuu * W0 + uv2 * qx - w2 * cx);
+        vy = vy - (wwuu * W1 + uv2 * qy - w2 * cy);
+        vz = vz - (wwuu * W2 + uv2 * qz - w2 * cz);
+    }
     const double dE = u[1], dR = u[2];
     // airspeed, angles, pressure: the value part of kite_rhs<Dual>
     const double V2 = vx * vx + vy * vy + vz * vz;

@@ -1472,15 +1472,15 @@ int ident_rows_ok(const kite_params* params, int32_t nparams, bool contain) {
 }
 
 int ident_run_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, const kite::IdentConst& K, const double* d_rows,
-                     const double* d_X, const double* d_U, double* d_out, double* d_cost2, int32_t* d_evals,
-                     int32_t* d_status, double* ws) {
+                     const double* d_X, const double* d_U, const double* d_W, double* d_out, double* d_cost2,
+                     int32_t* d_evals, int32_t* d_status, double* ws) {
     double* state = ws;
     double* slab = ws + (size_t)K.count * kite::ID_STATE;
     hipStream_t s = ctx->stream;
     for (int it = 0; it < cfg->iters; ++it) {
         const int first = it == 0;
         HIP_TRY(kite::launch_ident_accum(K, d_rows, first ? nullptr : state + kite::ID_S_PT, kite::ID_STATE,
-                                         first ? nullptr : state, d_X, d_U, slab, s));
+                                         first ? nullptr : state, d_X, d_U, d_W, slab, s));
         HIP_TRY(kite::launch_ident_solve(K, first, 0, d_rows, nullptr, slab, state, nullptr, nullptr, nullptr, d_out,
                                          d_cost2, d_evals, d_status, s));
     }
@@ -1496,24 +1496,34 @@ int64_t kite_nmpc_ident_workspace_doubles(const kite_ident_config* cfg, int32_t 
     return (int64_t)count * kite::ID_STATE + (int64_t)count * K.nchunks * kite::ID_SLAB;
 }
 
-int kite_nmpc_ident_sens(kite_nmpc_ctx* ctx, int32_t count, double h, int32_t substeps, const kite_params* params,
-                         int32_t nparams, const double* x13, const double* u3, double* x13_out, double* S) {
+// a NULL wind runs the windless kernels: the windless entries are these with NULL
+int kite_nmpc_ident_sens_wind(kite_nmpc_ctx* ctx, int32_t count, double h, int32_t substeps, const kite_params* params,
+                              int32_t nparams, const double* x13, const double* u3, const double* w3, double* x13_out,
+                              double* S) {
     if (!ctx || count < 1 || !x13 || !u3 || !x13_out || !S || (nparams != 1 && nparams != count)) return KITE_EINVAL;
     if (!std::isfinite(h) || !(h > 0.0) || substeps < 1 || substeps > 64) return KITE_EINVAL;
     const int rc = ident_rows_ok(params, nparams, false);
     if (rc) return rc;
     const size_t c = count;
-    return run_items(ctx, {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {x13, c * 13}, {u3, c * 3}},
+    return run_items(ctx,
+                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {x13, c * 13}, {u3, c * 3},
+                      {w3, w3 ? c * 3 : 0}},
                      {{x13_out, c * 13}, {S, c * 13 * KITE_IDENT_NP}},
                      [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_ident_sens(count, nparams, h / substeps, substeps, i[0], i[1], i[2], o[0],
-                                                        o[1], s);
+                         return kite::launch_ident_sens(count, nparams, h / substeps, substeps, i[0], i[1], i[2],
+                                                        w3 ? i[3] : nullptr, o[0], o[1], s);
                      });
 }
 
-int kite_nmpc_ident_normal(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
-                           const kite_params* params, int32_t nparams, const double* p21, const double* X,
-                           const double* U, double* A, double* g, double* cost, int32_t* status) {
+int kite_nmpc_ident_sens(kite_nmpc_ctx* ctx, int32_t count, double h, int32_t substeps, const kite_params* params,
+                         int32_t nparams, const double* x13, const double* u3, double* x13_out, double* S) {
+    return kite_nmpc_ident_sens_wind(ctx, count, h, substeps, params, nparams, x13, u3, nullptr, x13_out, S);
+}
+
+int kite_nmpc_ident_normal_wind(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                                const kite_params* params, int32_t nparams, const double* p21, const double* X,
+                                const double* U, const double* W, double* A, double* g, double* cost,
+                                int32_t* status) {
     if (!ctx || !p21 || !X || !U || !A || !g || !cost) return KITE_EINVAL;
     kite::IdentConst K;
     int rc = make_ident_const(cfg, count, T, nparams, &K);
@@ -1523,12 +1533,13 @@ int kite_nmpc_ident_normal(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int
     const size_t c = count, NPq = KITE_IDENT_NP;
     return run_items(ctx,
                      {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {p21, c * NPq},
-                      {X, c * (T + 1) * 13}, {U, c * T * 3}},
+                      {X, c * (T + 1) * 13}, {U, c * T * 3}, {W, W ? c * T * 3 : 0}},
                      {{A, c * NPq * NPq}, {g, c * NPq}, {cost, c}, {nullptr, (c + 1) / 2},
                       {nullptr, c * K.nchunks * kite::ID_SLAB}},
                      [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
                          int32_t* dst = reinterpret_cast<int32_t*>(o[3]);
-                         hipError_t e = kite::launch_ident_accum(K, i[0], i[1], KITE_IDENT_NP, nullptr, i[2], i[3], o[4], s);
+                         hipError_t e = kite::launch_ident_accum(K, i[0], i[1], KITE_IDENT_NP, nullptr, i[2], i[3],
+                                                                 W ? i[4] : nullptr, o[4], s);
                          if (e != hipSuccess) return e;
                          e = kite::launch_ident_solve(K, 0, 1, i[0], i[1], o[4], nullptr, o[0], o[1], o[2], nullptr,
                                                       nullptr, nullptr, dst, s);
@@ -1537,21 +1548,36 @@ int kite_nmpc_ident_normal(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int
                      });
 }
 
-int kite_nmpc_identify_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
-                              const double* d_params, int32_t nparams, const double* d_X, const double* d_U,
-                              double* d_params_out, double* d_cost2, int32_t* d_evals, int32_t* d_status,
-                              double* d_workspace) {
+int kite_nmpc_ident_normal(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                           const kite_params* params, int32_t nparams, const double* p21, const double* X,
+                           const double* U, double* A, double* g, double* cost, int32_t* status) {
+    return kite_nmpc_ident_normal_wind(ctx, cfg, count, T, params, nparams, p21, X, U, nullptr, A, g, cost, status);
+}
+
+int kite_nmpc_identify_wind_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                                   const double* d_params, int32_t nparams, const double* d_X, const double* d_U,
+                                   const double* d_W, double* d_params_out, double* d_cost2, int32_t* d_evals,
+                                   int32_t* d_status, double* d_workspace) {
     if (!ctx || !d_params || !d_X || !d_U || !d_params_out || !d_workspace) return KITE_EINVAL;
     kite::IdentConst K;
     const int rc = make_ident_const(cfg, count, T, nparams, &K);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    return ident_run_device(ctx, cfg, K, d_params, d_X, d_U, d_params_out, d_cost2, d_evals, d_status, d_workspace);
+    return ident_run_device(ctx, cfg, K, d_params, d_X, d_U, d_W, d_params_out, d_cost2, d_evals, d_status,
+                            d_workspace);
 }
 
-int kite_nmpc_identify(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
-                       const kite_params* params, int32_t nparams, const double* X, const double* U,
-                       kite_params* params_out, double* cost2, int32_t* evals, int32_t* status) {
+int kite_nmpc_identify_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                              const double* d_params, int32_t nparams, const double* d_X, const double* d_U,
+                              double* d_params_out, double* d_cost2, int32_t* d_evals, int32_t* d_status,
+                              double* d_workspace) {
+    return kite_nmpc_identify_wind_device(ctx, cfg, count, T, d_params, nparams, d_X, d_U, nullptr, d_params_out,
+                                          d_cost2, d_evals, d_status, d_workspace);
+}
+
+int kite_nmpc_identify_wind(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                            const kite_params* params, int32_t nparams, const double* X, const double* U,
+                            const double* W, kite_params* params_out, double* cost2, int32_t* evals, int32_t* status) {
     if (!ctx || !X || !U || !params_out) return KITE_EINVAL;
     kite::IdentConst K;
     int rc = make_ident_const(cfg, count, T, nparams, &K);
@@ -1563,12 +1589,13 @@ int kite_nmpc_identify(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t
     // int32 outputs (evals, status) share one scratch block of c doubles
     return run_items(ctx,
                      {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {X, c * (T + 1) * 13},
-                      {U, c * T * 3}},
+                      {U, c * T * 3}, {W, W ? c * T * 3 : 0}},
                      {{reinterpret_cast<double*>(params_out), c * 52}, {cost2, 2 * c}, {nullptr, c}, {nullptr, ws}},
                      [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
                          int32_t* dev = reinterpret_cast<int32_t*>(o[2]);
                          int32_t* dst = dev + c;
-                         if (ident_run_device(ctx, cfg, K, i[0], i[1], i[2], o[0], o[1], dev, dst, o[3]) != KITE_OK)
+                         if (ident_run_device(ctx, cfg, K, i[0], i[1], i[2], W ? i[3] : nullptr, o[0], o[1], dev, dst,
+                                              o[3]) != KITE_OK)
                              return hipErrorLaunchFailure;
                          if (evals) {
                              hipError_t e = hipMemcpyAsync(evals, dev, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
@@ -1577,6 +1604,13 @@ int kite_nmpc_identify(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t
                          if (status) return hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
                          return hipSuccess;
                      });
+}
+
+int kite_nmpc_identify(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t count, int32_t T,
+                       const kite_params* params, int32_t nparams, const double* X, const double* U,
+                       kite_params* params_out, double* cost2, int32_t* evals, int32_t* status) {
+    return kite_nmpc_identify_wind(ctx, cfg, count, T, params, nparams, X, U, nullptr, params_out, cost2, evals,
+                                   status);
 }
 
 int kite_nmpc_rk4_sens(kite_nmpc_ctx* ctx, int32_t count, const double* x15, const double* u4, double tf,

@@ -34,7 +34,12 @@ One step of a fleet of kites on one rank:
          all on the stream.  With ``estimator_model="controller"`` the
          estimator filters with those models too (kite_nmpc_set_estimator_model),
          from the step after the identification on; the default keeps the
-         creation model in the filter.
+         creation model in the filter.  With ``ident_wind`` (and a
+         ``FlightRecorder(..., wind=True)``) the wind of each period is logged
+         next to the control -- a known (B, 3) wind, or with ``"estimate"`` the
+         wind EKF's estimate as the controller received it -- and the
+         identification fits the model that sees it
+         (kite_nmpc_identify_wind_device).
 
 The stepper does the arithmetic; ``GpuStepper`` drives libkite_nmpc.so on
 device tensors.  Tests plug a CPU oracle stepper into the same loop to check
@@ -94,10 +99,12 @@ class GpuStepper:
         """The (B, 52) rows in force, on the host."""
         return self.ctx.get_params()
 
-    def identify(self, config, T, rows, X, U, out, cost2, evals, status, ws):
-        """kite_nmpc_identify_device on device tensors, a row per kite."""
+    def identify(self, config, T, rows, X, U, out, cost2, evals, status, ws, W=None):
+        """kite_nmpc_identify_device on device tensors, a row per kite; W: the
+        wind log (B, T, 3) (kite_nmpc_identify_wind_device), None: windless."""
         self.ctx.identify_device(config, rows.shape[0], T, rows.data_ptr(), rows.shape[0], X.data_ptr(), U.data_ptr(),
-                                 out.data_ptr(), cost2.data_ptr(), evals.data_ptr(), status.data_ptr(), ws.data_ptr())
+                                 out.data_ptr(), cost2.data_ptr(), evals.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                 wind=W.data_ptr() if W is not None else 0)
 
 
 class GpuPlant:
@@ -121,13 +128,17 @@ class FlightRecorder:
     (``BatchNMPC.identify_device``): X (B, T+1, 13) the kite state handed to the
     controller at the start of each control period, U (B, T, 3) the control
     (T, dE, dR) applied over it.  ``FleetLoop(recorder=...)`` fills it, one
-    period per step, and it stops when full (``full``)."""
+    period per step, and it stops when full (``full``).  With ``wind=True`` it
+    also owns W (B, T, 3), the known world-frame wind of each period
+    (``record_wind``, next to ``record_control``), and ``identify`` fits the
+    model that sees that wind (kite_nmpc_identify_wind_device)."""
 
-    def __init__(self, B: int, T: int, device=None):
+    def __init__(self, B: int, T: int, device=None, wind: bool = False):
         f64 = dict(dtype=torch.float64, device=device)
         self.B, self.T = int(B), int(T)
         self.X = torch.zeros((self.B, self.T + 1, 13), **f64)
         self.U = torch.zeros((self.B, self.T, 3), **f64)
+        self.W = torch.zeros((self.B, self.T, 3), **f64) if wind else None
         self.nx = 0            # states recorded
         self.nu = 0            # controls recorded
 
@@ -142,6 +153,14 @@ class FlightRecorder:
         if self.nx <= self.T:
             self.X[:, self.nx, :].copy_(x0[:, :13])
             self.nx += 1
+
+    def record_wind(self, w3: torch.Tensor) -> None:
+        """The wind (B, 3) of the period whose control comes next: row ``nu``,
+        so call it before that period's ``record_control``."""
+        if self.W is None:
+            raise ValueError("the recorder logs no wind: FlightRecorder(..., wind=True)")
+        if self.nu < self.T:
+            self.W[:, self.nu, :].copy_(w3)
 
     def record_control(self, u0: torch.Tensor) -> None:
         if self.nu < self.T:
@@ -169,7 +188,7 @@ class FlightRecorder:
         ws = torch.empty((nmpc.ident_workspace_doubles(config, self.B, self.T),), dtype=torch.float64, device=dev)
         ctx.identify_device(config, self.B, self.T, rows.data_ptr(), rows.shape[0], self.X.data_ptr(),
                             self.U.data_ptr(), out.data_ptr(), cost2.data_ptr(), evals.data_ptr(), status.data_ptr(),
-                            ws.data_ptr())
+                            ws.data_ptr(), wind=self.W.data_ptr() if self.W is not None else 0)
         self._keep = (rows, ws)      # alive until the stream has run the launches
         return out, cost2, evals, status
 
@@ -207,7 +226,7 @@ class FleetLoop:
     def __init__(self, stepper, x0: torch.Tensor, N: int, dt: float, ekf: bool = False, ekf_substeps: int = 5,
                  covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None,
                  plant=None, wind_ekf: bool = False, wind_max: float = 20.0, recorder=None, adapt=None,
-                 estimator_model: str = "creation"):
+                 estimator_model: str = "creation", ident_wind=None):
         if ekf and wind_ekf:
             raise ValueError("ekf and wind_ekf are two estimators: choose one")
         if estimator_model not in ("creation", "controller"):
@@ -216,6 +235,13 @@ class FleetLoop:
             raise ValueError('estimator_model="controller" needs an estimator: ekf=True or wind_ekf=True')
         if adapt is not None and recorder is None:
             raise ValueError("adapt identifies from a flight log: give the loop a recorder")
+        if isinstance(ident_wind, str):
+            if ident_wind != "estimate":
+                raise ValueError('ident_wind is None, a (B, 3) tensor or "estimate"')
+            if not wind_ekf:
+                raise ValueError('ident_wind="estimate" logs the wind EKF\'s estimate: it needs wind_ekf=True')
+        if ident_wind is not None and (recorder is None or getattr(recorder, "W", None) is None):
+            raise ValueError("ident_wind is logged by the recorder: give the loop a FlightRecorder(..., wind=True)")
         B = x0.shape[0]
         dev = x0.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -276,6 +302,16 @@ class FleetLoop:
         # controller's per-kite models, all on the stream (``_adapt``)
         self.adapt = adapt
         self.adapt_count = 0
+        # the wind the identification's model sees, logged each period next to the
+        # control: None (no wind log), a known (B, 3) wind, or "estimate": the
+        # wind in force for the controller this period, which is the wind EKF's
+        # estimate as kite_nmpc_set_wind_device treats it (a non-finite
+        # component 0, each clamped to +-wind_max)
+        self.ident_wind = ident_wind
+        if ident_wind is not None and not isinstance(ident_wind, str):
+            if tuple(ident_wind.shape) != (B, 3):
+                raise ValueError(f"ident_wind: a (B, 3) = ({B}, 3) tensor, got {tuple(ident_wind.shape)}")
+            self.ident_wind = ident_wind.to(**f64).clone()
         if adapt is not None:
             from . import nmpc
             if recorder.B != B:
@@ -332,8 +368,12 @@ class FleetLoop:
         rejected there, ``params_status``); the log starts again with the state
         at hand.  This step's RTI already predicts with the new models."""
         rec = self.recorder
-        self.stepper.identify(self.adapt, rec.T, self.model_rows, rec.X, rec.U, self.ident_rows, self.ident_cost2,
-                              self.ident_evals, self.ident_status, self._ident_ws)
+        if getattr(rec, "W", None) is not None:
+            self.stepper.identify(self.adapt, rec.T, self.model_rows, rec.X, rec.U, self.ident_rows, self.ident_cost2,
+                                  self.ident_evals, self.ident_status, self._ident_ws, W=rec.W)
+        else:
+            self.stepper.identify(self.adapt, rec.T, self.model_rows, rec.X, rec.U, self.ident_rows,
+                                  self.ident_cost2, self.ident_evals, self.ident_status, self._ident_ws)
         conv, nan = self._ident_ok
         ok = ((self.ident_status & conv) != 0) & ((self.ident_status & nan) == 0)
         self.model_rows.copy_(torch.where(ok[:, None], self.ident_rows, self.model_rows))
@@ -374,6 +414,12 @@ class FleetLoop:
                 self._adapt()
         self.stepper.rti(self.x0, self.u0, self.traj, self.diag, self.status)
         if self.recorder is not None:
+            if self.ident_wind is not None:
+                if isinstance(self.ident_wind, str):
+                    w = torch.nan_to_num(self.xe[:, 13:16], nan=0.0, posinf=0.0, neginf=0.0)
+                    self.recorder.record_wind(w.clamp(-self.wind_max, self.wind_max))
+                else:
+                    self.recorder.record_wind(self.ident_wind)
             self.recorder.record_control(self.u0)
         if self.pub is not None:
             self.gathered = self.pub.publish(self.u0, self.diag)

@@ -226,6 +226,19 @@ _SIGNATURES = {
                                                  ctypes.c_void_p, ctypes.c_void_p]),
     "kite_nmpc_ident_workspace_doubles": (ctypes.c_int64, [ctypes.POINTER(IdentConfig), ctypes.c_int32,
                                                            ctypes.c_int32]),
+    "kite_nmpc_ident_sens_wind": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+                                                 ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, _DP, _DP]),
+    "kite_nmpc_ident_normal_wind": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IdentConfig), ctypes.c_int32,
+                                                   ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, _DP,
+                                                   _DP, _DP, _DP, _IP]),
+    "kite_nmpc_identify_wind": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IdentConfig), ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP,
+                                               ctypes.c_void_p, _DP, _IP, _IP]),
+    "kite_nmpc_identify_wind_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IdentConfig), ctypes.c_int32,
+                                                      ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p]),
     "kite_nmpc_plant_set_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "kite_nmpc_plant_set_wind": (ctypes.c_int, [ctypes.c_void_p, _DP]),
     "kite_nmpc_plant_step": (ctypes.c_int, [ctypes.c_void_p, _DP, _DP, ctypes.c_double, ctypes.c_double,
@@ -769,21 +782,47 @@ class BatchNMPC:
             raise ValueError("identification parameters: 52 values, one row or one per kite")
         return p
 
-    def ident_sens(self, x13, u3, h: float, substeps: int = 4, params=None):
+    @staticmethod
+    def _ident_wind(wind, B: int, T: Optional[int]) -> np.ndarray:
+        """The wind of the identification as a contiguous array: (B, 3) for
+        ``ident_sens`` (T None), else the log (B, T, 3); there a (B, 3) array is
+        one wind per kite, held over its T samples."""
+        w = _f64(wind)
+        if T is None:
+            if w.shape != (B, 3):
+                raise ValueError(f"wind: (count, 3) = ({B}, 3), got {w.shape}")
+            return w
+        if w.shape == (B, 3):
+            w = np.ascontiguousarray(np.broadcast_to(w[:, None, :], (B, T, 3)))
+        if w.shape != (B, T, 3):
+            raise ValueError(f"wind: (B, T, 3) = ({B}, {T}, 3) or (B, 3), got {w.shape}")
+        return w
+
+    def ident_sens(self, x13, u3, h: float, substeps: int = 4, params=None, wind=None):
         """One sample interval per item (kite_nmpc_ident_sens): x+ (count, 13) and
-        S = d x+ / d p (count, 13, 21, unscaled) with respect to ``IDENT_FIELDS``."""
+        S = d x+ / d p (count, 13, 21, unscaled) with respect to ``IDENT_FIELDS``.
+        wind (count, 3): the item's world-frame wind (kite_nmpc_ident_sens_wind);
+        None: the windless model."""
         x = _f64(x13).reshape(-1, 13); u = _f64(u3).reshape(-1, 3)
         c = x.shape[0]
         p = self._ident_rows(params, c)
         xo = np.zeros((c, 13)); S = np.zeros((c, 13, IDENT_NP))
+        if wind is not None:
+            w = self._ident_wind(wind, c, None)
+            _check(lib().kite_nmpc_ident_sens_wind(self._h, c, float(h), int(substeps),
+                                                   ctypes.c_void_p(p.ctypes.data), p.shape[0], _p(x), _p(u), _p(w),
+                                                   _p(xo), _p(S)), "ident_sens_wind")
+            return xo, S
         _check(lib().kite_nmpc_ident_sens(self._h, c, float(h), int(substeps), ctypes.c_void_p(p.ctypes.data),
                                           p.shape[0], _p(x), _p(u), _p(xo), _p(S)), "ident_sens")
         return xo, S
 
-    def ident_normal(self, X, U, p21, params=None, config: Optional[IdentConfig] = None):
+    def ident_normal(self, X, U, p21, params=None, config: Optional[IdentConfig] = None, wind=None):
         """One evaluation of the identification's normal equations at the
         parameter values p21 (B, 21) on the logs X (B, T+1, 13), U (B, T, 3):
-        (A (B, 21, 21), g (B, 21), cost (B,), status (B,)) in the scaled variables."""
+        (A (B, 21, 21), g (B, 21), cost (B,), status (B,)) in the scaled variables.
+        wind: the logged world-frame wind (B, T, 3), or (B, 3) held over the log
+        (kite_nmpc_ident_normal_wind); None: the windless model."""
         cfg = config if config is not None else ident_default_config()
         X = _f64(X); U = _f64(U)
         B, T = U.shape[0], U.shape[1]
@@ -793,16 +832,25 @@ class BatchNMPC:
         q = _f64(p21).reshape(B, IDENT_NP)
         A = np.zeros((B, IDENT_NP, IDENT_NP)); g = np.zeros((B, IDENT_NP)); cost = np.zeros(B)
         st = np.zeros(B, dtype=np.int32)
+        if wind is not None:
+            w = self._ident_wind(wind, B, T)
+            _check(lib().kite_nmpc_ident_normal_wind(self._h, ctypes.byref(cfg), B, T, ctypes.c_void_p(p.ctypes.data),
+                                                     p.shape[0], _p(q), _p(X), _p(U), _p(w), _p(A), _p(g), _p(cost),
+                                                     st.ctypes.data_as(_IP)), "ident_normal_wind")
+            return A, g, cost, st
         _check(lib().kite_nmpc_ident_normal(self._h, ctypes.byref(cfg), B, T, ctypes.c_void_p(p.ctypes.data),
                                             p.shape[0], _p(q), _p(X), _p(U), _p(A), _p(g), _p(cost),
                                             st.ctypes.data_as(_IP)), "ident_normal")
         return A, g, cost, st
 
-    def identify(self, X, U, params=None, config: Optional[IdentConfig] = None) -> IdentResult:
+    def identify(self, X, U, params=None, config: Optional[IdentConfig] = None, wind=None) -> IdentResult:
         """Fit the 21 aerodynamic coefficients (``IDENT_FIELDS``) of every kite to
         its log X (B, T+1, 13), U (B, T, 3) (kite_nmpc_identify).  params: the
         kites' rows (52 values, one for all or (B, 52)), whose 21 are the start
-        and the centre of the box; None: the context's own."""
+        and the centre of the box; None: the context's own.  wind: the known
+        world-frame wind the log was flown under, (B, T, 3) with row k held over
+        sample interval k, or (B, 3) held over the log (kite_nmpc_identify_wind);
+        None: the windless model."""
         cfg = config if config is not None else ident_default_config()
         X = _f64(X); U = _f64(U)
         B, T = U.shape[0], U.shape[1]
@@ -811,6 +859,13 @@ class BatchNMPC:
         p = self._ident_rows(params, B)
         out = np.zeros((B, len(_PARAM_FIELDS))); c2 = np.zeros((B, 2))
         ev = np.zeros(B, dtype=np.int32); st = np.zeros(B, dtype=np.int32)
+        if wind is not None:
+            w = self._ident_wind(wind, B, T)
+            _check(lib().kite_nmpc_identify_wind(self._h, ctypes.byref(cfg), B, T, ctypes.c_void_p(p.ctypes.data),
+                                                 p.shape[0], _p(X), _p(U), _p(w), ctypes.c_void_p(out.ctypes.data),
+                                                 _p(c2), ev.ctypes.data_as(_IP), st.ctypes.data_as(_IP)),
+                   "identify_wind")
+            return IdentResult(out, c2[:, 0].copy(), c2[:, 1].copy(), ev, st)
         _check(lib().kite_nmpc_identify(self._h, ctypes.byref(cfg), B, T, ctypes.c_void_p(p.ctypes.data), p.shape[0],
                                         _p(X), _p(U), ctypes.c_void_p(out.ctypes.data), _p(c2),
                                         ev.ctypes.data_as(_IP), st.ctypes.data_as(_IP)), "identify")
@@ -818,11 +873,19 @@ class BatchNMPC:
 
     def identify_device(self, config: IdentConfig, count: int, T: int, params_ptr: int, nparams: int, X_ptr: int,
                         U_ptr: int, params_out_ptr: int, cost2_ptr: int = 0, evals_ptr: int = 0, status_ptr: int = 0,
-                        workspace_ptr: int = 0):
+                        workspace_ptr: int = 0, wind: int = 0):
         """identify on device pointers (kite_nmpc_identify_device): 2 * iters
         launches on the context stream, nothing allocated, copied or awaited;
-        the workspace holds ``ident_workspace_doubles`` doubles."""
+        the workspace holds ``ident_workspace_doubles`` doubles.  wind: device
+        pointer of the wind log (count, T, 3) (kite_nmpc_identify_wind_device);
+        0: the windless model."""
         v = lambda p: ctypes.c_void_p(p) if p else None
+        if wind:
+            _check(lib().kite_nmpc_identify_wind_device(self._h, ctypes.byref(config), int(count), int(T),
+                                                        v(params_ptr), int(nparams), v(X_ptr), v(U_ptr), v(wind),
+                                                        v(params_out_ptr), v(cost2_ptr), v(evals_ptr), v(status_ptr),
+                                                        v(workspace_ptr)), "identify_wind_device")
+            return
         _check(lib().kite_nmpc_identify_device(self._h, ctypes.byref(config), int(count), int(T), v(params_ptr),
                                                int(nparams), v(X_ptr), v(U_ptr), v(params_out_ptr), v(cost2_ptr),
                                                v(evals_ptr), v(status_ptr), v(workspace_ptr)), "identify_device")

@@ -1,7 +1,7 @@
 """The identification's kernels at fleet size, beside k_rk4_sens2 of the headline step.
 
-    python tools/ident_probe.py [B] [T] [reps]
-    rocprofv3 --kernel-trace --stats -d DIR -- python tools/ident_probe.py
+    python tools/ident_probe.py [--wind] [B] [T] [reps]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/ident_probe.py [--wind]
 
 At batch B (default 4096) it flies T = 100 samples of h = 0.02 per kite on the
 plant simulator (per-kite aerodynamic coefficients +-10 %, sinusoidal thrust,
@@ -14,6 +14,10 @@ durations come from the trace's statistics; per unit of work
 The script itself prints stream-event times (launch overhead included), what
 the fit reached, and the host time of the numpy reference (tests/ident_ref.py)
 for one kite and one evaluation, for scale.
+
+With --wind every kite's plant flies under its own constant wind (+-1.5 m/s per
+axis, no gust), the wind log holds it in every row, and the identification is
+the wind form (kite_nmpc_identify_wind_device: k_ident_accum_w in the trace).
 """
 import json
 import os
@@ -27,9 +31,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import openkite_amd as ok  # noqa: E402
 from bench import synthetic_x0  # noqa: E402
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-T = int(sys.argv[2]) if len(sys.argv) > 2 else 100
-REPS = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+WIND = "--wind" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a != "--wind"]
+B = int(ARGS[0]) if len(ARGS) > 0 else 4096
+T = int(ARGS[1]) if len(ARGS) > 1 else 100
+REPS = int(ARGS[2]) if len(ARGS) > 2 else 5
 H, SUB, ITERS = 0.02, 4, 8
 
 cfg = ok.default_config(N=20)
@@ -56,6 +62,11 @@ def timed(fn, reps=REPS):
 # the logs: every kite's own plant under sinusoidal controls
 truth = ok.perturb_params(kp, B, 0.1, 5, fields=ok.IDENT_FIELDS)
 g.plant_set_params(truth)
+Wd = None
+if WIND:
+    wind = np.random.default_rng(8).uniform(-1.5, 1.5, (B, 3))
+    g.plant_set_wind(wind=wind)
+    Wd = torch.from_numpy(np.ascontiguousarray(np.repeat(wind[:, None], T, axis=1))).cuda()          # (B, T, 3)
 rng = np.random.default_rng(6)
 ph = rng.uniform(0, 2 * np.pi, (B, 3))
 t = np.arange(T) * H
@@ -85,10 +96,10 @@ ws = torch.empty((ok.ident_workspace_doubles(icfg, B, T),), **dev)
 
 def identify():
     g.identify_device(icfg, B, T, rows.data_ptr(), 1, X.data_ptr(), U.data_ptr(), out.data_ptr(), cost2.data_ptr(),
-                      evals.data_ptr(), status.data_ptr(), ws.data_ptr())
+                      evals.data_ptr(), status.data_ptr(), ws.data_ptr(), wind=Wd.data_ptr() if WIND else 0)
 
 
-res = {"B": B, "T": T, "substeps": SUB, "segment": 1, "iters": ITERS, "reps": REPS}
+res = {"B": B, "T": T, "substeps": SUB, "segment": 1, "iters": ITERS, "reps": REPS, "wind": WIND}
 res["identify_device_us"] = timed(identify)
 idx = [ok.ident_param_index(j) for j in range(ok.IDENT_NP)]
 sc = np.where(kp[idx] != 0.0, np.abs(kp[idx]), 1.0)
@@ -120,7 +131,11 @@ try:
     from tests import ident_ref as ref
     Xh, U0 = X[0].cpu().numpy(), Uh[0]
     t0 = time.perf_counter()
-    ref.normal(kp, kp[ref.IDX], Xh, np.ascontiguousarray(U0), icfg)
+    if WIND:
+        from tests import ident_wind_ref as wref
+        wref.normal(kp, kp[ref.IDX], Xh, np.ascontiguousarray(U0), Wd[0].cpu().numpy(), icfg)
+    else:
+        ref.normal(kp, kp[ref.IDX], Xh, np.ascontiguousarray(U0), icfg)
     res["numpy_reference_one_kite_one_evaluation_s"] = time.perf_counter() - t0
 except Exception as e:  # the oracle is test infrastructure: the probe runs without it
     res["numpy_reference_one_kite_one_evaluation_s"] = None
