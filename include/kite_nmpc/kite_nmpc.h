@@ -59,7 +59,10 @@ extern "C" {
                                       (kite_nmpc_set/get_estimator_model,
                                       KITE_EST_MODEL_*) and the identification under
                                       a logged wind (kite_nmpc_identify_wind[_device],
-                                      _ident_normal_wind, _ident_sens_wind)       */
+                                      _ident_normal_wind, _ident_sens_wind) and the
+                                      kinematic EKF (kite_nmpc_kinekf_step[_device],
+                                      _kinekf_init[_device], _jacobian_kin,
+                                      kite_pose_frame, KITE_EKF_INIT_BAD)         */
 #define KITE_PATH_MAX_HARMONICS 8 /* Fourier path: harmonics per axis              */
 
 /* ---- error codes ------------------------------------------------------ */
@@ -410,6 +413,71 @@ int kite_nmpc_jacobian_wind(kite_nmpc_ctx* ctx, int32_t count, const double* x13
  * KITE_EINVAL.                                                              */
 int kite_nmpc_set_wind_device(kite_nmpc_ctx* ctx, const double* d_wind, int32_t stride, double wmax);
 
+/* ---- kinematic (pose-only) EKF (build extension; additive, no version change)
+ * The filter the reference's estimator node flies (ekf_node.cpp:235-241):
+ * KiteEKF(Function, Function) (kiteEKF.cpp:54-72) over RigidBodyKinematics
+ * (kite.cpp:622-661).  It has no aerodynamic model, no control and no
+ * parameters: v_b and w_b are random walks, r' = vec(q (x) [0, v_b] (x)
+ * conj(q)), q' = 1/2 q (x) [0, w_b] + 1/2 lambda q (q.q - 1) with lambda = -10,
+ * and the 7 pose components are measured, H = [0_{7x6} I_7].  x13 (count x 13)
+ * and P169 (count x 13 x 13, row-major) are updated in place; W169 / V49
+ * (kite_ekf_default_covariances: the reference uses the same defaults in all
+ * three constructors) are shared by all kites.  One call:
+ *   with a frame:  z <- frame(z), on a copy (the caller's z7 is never written)
+ *   with z7:       the copy's quaternion is negated when z_q . q_est < 0 at
+ *                  entry (q and -q are one attitude; motion capture flips)
+ *   `substeps` propagations of dt / substeps: A = I + J(x) h with the
+ *                  closed-form J, one RK4 step, P = A P A' + W169
+ *   with z7:       one update as kite_nmpc_windekf_step does it, then
+ *                  P <- (P + P') / 2
+ * Deviations from the reference: RK4 over the dt given (the reference's CVODES
+ * integrates over a fixed 0.02 s whatever the filter's dt, kite.cpp:656-659
+ * against kiteEKF.cpp:83-93); the quaternion sign alignment; the symmetrised P.
+ * status (count words, nullable) receives KITE_EKF_NAN / KITE_EKF_S_NOT_PD,
+ * written (not OR-ed) on every call, with kite_nmpc_windekf_step's meaning; a
+ * non-finite measurement counts as a bad update (KITE_EKF_S_NOT_PD: the
+ * propagated estimate is kept), not as a NaN kite.  count < 1, dt <= 0 or
+ * non-finite, substeps < 1 or > 2^24, a zero-norm or non-finite frame
+ * rotation: KITE_EINVAL.  kite_nmpc_set_estimator_model does not touch this
+ * filter: it has no model.                                                   */
+/* The motion-capture -> world change of a measured pose (optitrack2world,
+ * ekf_node.cpp:148-169), z7 = (r, q):
+ *   r <- r + vec(q (x) [0, offset] (x) conj(q))
+ *   r <- vec(rotation (x) [0, r] (x) conj(rotation)) + shift
+ *   q <- rotation (x) q (x) conj(rotation)
+ * A NULL frame in the calls below means the poses are world poses already.   */
+typedef struct { double offset[3]; double rotation[4]; double shift[3]; } kite_pose_frame;
+/* the node's: offset (-0.09, 0, -0.02), rotation (0, -1, 0, 0), shift (0, 0, 2.77) */
+void kite_pose_frame_default(kite_pose_frame* frame);
+int kite_nmpc_kinekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, double* x13,
+                          double* P169, const double* z7, const double* W169, const double* V49,
+                          const kite_pose_frame* frame, int32_t* status);
+/* Same on device pointers, asynchronous on the context stream; frame is a
+ * host struct, passed by value into the launch.                             */
+int kite_nmpc_kinekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps,
+                                 double* d_x13, double* d_P169, const double* d_z7, const double* d_W169,
+                                 const double* d_V49, const kite_pose_frame* frame, int32_t* d_status);
+/* The 13 states from two consecutive poses dt apart (KiteEKF_Node::initialize,
+ * ekf_node.cpp:68-132), both through `frame` when one is given:
+ *   rdot = (r_new - r_prev) / dt,  v_b = vec(conj(q_prev) (x) [0, rdot] (x) q_prev)
+ *   dq = conj(q_prev) (x) q_new,   w_b = (2 / dt) vec(dq - [1, 0, 0, 0])
+ *   x13 = [v_b, w_b, pose_new]
+ * One deviation: q_new is negated for dq when q_prev . q_new < 0; the state
+ * keeps pose_new as measured.  Per kite, dt <= 0 or non-finite or a
+ * non-finite pose sets KITE_EKF_INIT_BAD in status (count words, nullable,
+ * written on every call) and leaves that kite's x13 untouched; so dt is not
+ * an argument error here.  count < 1 or a bad frame rotation: KITE_EINVAL.   */
+#define KITE_EKF_INIT_BAD 4
+int kite_nmpc_kinekf_init(kite_nmpc_ctx* ctx, int32_t count, double dt, const double* pose_prev7,
+                          const double* pose_new7, const kite_pose_frame* frame, double* x13_out,
+                          int32_t* status);
+int kite_nmpc_kinekf_init_device(kite_nmpc_ctx* ctx, int32_t count, double dt, const double* d_pose_prev7,
+                                 const double* d_pose_new7, const kite_pose_frame* frame, double* d_x13_out,
+                                 int32_t* d_status);
+/* The filter's Jacobian pass: J (count x 13 x 13, row-major) = df/dx of the
+ * kinematic model at x13; rows 0..5 are zero.                                */
+int kite_nmpc_jacobian_kin(kite_nmpc_ctx* ctx, int32_t count, const double* x13, double* J169);
+
 /* ---- per-kite controller models (build extension; additive, no version change)
  * The model of the controller's predictions, per kite: the batch dimension
  * "one airframe per instance", and the way identified parameters
@@ -466,7 +534,8 @@ int kite_nmpc_get_params(kite_nmpc_ctx* ctx, kite_params* out);
  * kite_nmpc_set_params_device sees the new rows without synchronisation.
  * Rows equal to the creation row give the creation model's estimates bit for
  * bit.  The item-wise entry points (kite_nmpc_jacobian_wind among them) keep
- * the creation model.  Any other mode: KITE_EINVAL.                          */
+ * the creation model.  The kinematic filter (kite_nmpc_kinekf_step[_device])
+ * is not touched: it has no model.  Any other mode: KITE_EINVAL.             */
 #define KITE_EST_MODEL_CREATION   0
 #define KITE_EST_MODEL_CONTROLLER 1
 int kite_nmpc_set_estimator_model(kite_nmpc_ctx* ctx, int32_t mode);

@@ -20,6 +20,7 @@
 
 #include "kite_nmpc/kite_nmpc.h"
 #include "ident_kernels.hpp"
+#include "kin_model.hpp"
 #include "kite_model_dp.hpp"
 #include "rti_kernels.hpp"
 
@@ -1312,6 +1313,126 @@ int kite_nmpc_set_wind_device(kite_nmpc_ctx* ctx, const double* d_wind, int32_t 
         ++ctx->graph_gen;
     }
     return KITE_OK;
+}
+
+// ---- kinematic (pose-only) EKF (kinekf_kernels.hip) ---------------------------
+void kite_pose_frame_default(kite_pose_frame* f) {
+    if (!f) return;
+    // ekf_node.cpp: brf_offset, brf_rotation and the +2.77 of optitrack2world (:166)
+    const kite_pose_frame d = {{-0.09, 0.0, -0.02}, {0.0, -1.0, 0.0, 0.0}, {0.0, 0.0, 2.77}};
+    *f = d;
+}
+
+extern "C++" {
+namespace {
+static_assert(sizeof(kite::PoseFrame) == sizeof(kite_pose_frame), "PoseFrame mirrors kite_pose_frame");
+// *use: the frame for the launch (nullptr without one); a rotation that is
+// non-finite or has no length is no rotation
+int pose_frame_arg(const kite_pose_frame* frame, kite::PoseFrame* F, const kite::PoseFrame** use) {
+    *use = nullptr;
+    if (!frame) return KITE_OK;
+    double n2 = 0.0;
+    for (int i = 0; i < 4; ++i) {
+        if (!std::isfinite(frame->rotation[i])) return KITE_EINVAL;
+        n2 += frame->rotation[i] * frame->rotation[i];
+    }
+    if (!(n2 > 0.0) || !std::isfinite(n2)) return KITE_EINVAL;
+    std::memcpy(F, frame, sizeof(*F));
+    *use = F;
+    return KITE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int kite_nmpc_kinekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, double* d_x13,
+                                 double* d_P169, const double* d_z7, const double* d_W169, const double* d_V49,
+                                 const kite_pose_frame* frame, int32_t* d_status) {
+    if (!ctx || !d_x13 || !d_P169 || !d_W169 || (d_z7 && !d_V49)) return KITE_EINVAL;
+    const int rc = windekf_args_ok(count, dt, substeps);
+    if (rc) return rc;
+    kite::PoseFrame F;
+    const kite::PoseFrame* use;
+    { const int rcf = pose_frame_arg(frame, &F, &use); if (rcf) return rcf; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(kite::launch_ekf_kin(count, dt, substeps, d_x13, d_P169, d_z7, d_W169, d_V49, use, d_status,
+                                 ctx->stream));
+    return KITE_OK;
+}
+
+int kite_nmpc_kinekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, double* x13, double* P169,
+                          const double* z7, const double* W169, const double* V49, const kite_pose_frame* frame,
+                          int32_t* status) {
+    if (!ctx || !x13 || !P169 || !W169 || (z7 && !V49)) return KITE_EINVAL;
+    const int rc0 = windekf_args_ok(count, dt, substeps);
+    if (rc0) return rc0;
+    kite::PoseFrame F;
+    const kite::PoseFrame* use;
+    { const int rcf = pose_frame_arg(frame, &F, &use); if (rcf) return rcf; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t c = count;
+    const size_t nx = c * 13, np = c * 169, nz = z7 ? c * 7 : 0, ns = (c + 1) / 2;
+    int rc = ensure_scratch(ctx, (nx + np + nz + 169 + 49 + ns) * sizeof(double));
+    if (rc) return rc;
+    double *dx = ctx->scratch, *dP = dx + nx, *dz = dP + np, *dW = dz + nz, *dV = dW + 169;
+    int32_t* dst = reinterpret_cast<int32_t*>(dV + 49);
+    hipStream_t s = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dx, x13, nx * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dP, P169, np * sizeof(double), hipMemcpyHostToDevice, s));
+    if (z7) HIP_TRY(hipMemcpyAsync(dz, z7, nz * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dW, W169, 169 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (V49) HIP_TRY(hipMemcpyAsync(dV, V49, 49 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(kite::launch_ekf_kin(count, dt, substeps, dx, dP, z7 ? dz : nullptr, dW, dV, use, dst, s));
+    HIP_TRY(hipMemcpyAsync(x13, dx, nx * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(P169, dP, np * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return KITE_OK;
+}
+
+int kite_nmpc_kinekf_init_device(kite_nmpc_ctx* ctx, int32_t count, double dt, const double* d_pose_prev7,
+                                 const double* d_pose_new7, const kite_pose_frame* frame, double* d_x13_out,
+                                 int32_t* d_status) {
+    if (!ctx || count < 1 || !d_pose_prev7 || !d_pose_new7 || !d_x13_out) return KITE_EINVAL;
+    kite::PoseFrame F;
+    const kite::PoseFrame* use;
+    { const int rcf = pose_frame_arg(frame, &F, &use); if (rcf) return rcf; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(kite::launch_ekf_kin_init(count, dt, d_pose_prev7, d_pose_new7, use, d_x13_out, d_status, ctx->stream));
+    return KITE_OK;
+}
+
+int kite_nmpc_kinekf_init(kite_nmpc_ctx* ctx, int32_t count, double dt, const double* pose_prev7,
+                          const double* pose_new7, const kite_pose_frame* frame, double* x13_out, int32_t* status) {
+    if (!ctx || count < 1 || !pose_prev7 || !pose_new7 || !x13_out) return KITE_EINVAL;
+    kite::PoseFrame F;
+    const kite::PoseFrame* use;
+    { const int rcf = pose_frame_arg(frame, &F, &use); if (rcf) return rcf; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t c = count;
+    const size_t nz = c * 7, nx = c * 13, ns = (c + 1) / 2;
+    int rc = ensure_scratch(ctx, (2 * nz + nx + ns) * sizeof(double));
+    if (rc) return rc;
+    double *dp = ctx->scratch, *dn = dp + nz, *dx = dn + nz;
+    int32_t* dst = reinterpret_cast<int32_t*>(dx + nx);
+    hipStream_t s = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dp, pose_prev7, nz * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dn, pose_new7, nz * sizeof(double), hipMemcpyHostToDevice, s));
+    // a kite that cannot be initialised keeps the caller's x13
+    HIP_TRY(hipMemcpyAsync(dx, x13_out, nx * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(kite::launch_ekf_kin_init(count, dt, dp, dn, use, dx, dst, s));
+    HIP_TRY(hipMemcpyAsync(x13_out, dx, nx * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return KITE_OK;
+}
+
+int kite_nmpc_jacobian_kin(kite_nmpc_ctx* ctx, int32_t count, const double* x13, double* J169) {
+    if (!ctx || count < 1 || !x13 || !J169) return KITE_EINVAL;
+    const size_t c = count;
+    return run_items(ctx, {{x13, c * 13}}, {{J169, c * 169}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         return kite::launch_jacobian_kin(count, i[0], o[0], s);
+                     });
 }
 
 // ---- per-kite controller models (k_model_const, rti_kernels.hip) -------------

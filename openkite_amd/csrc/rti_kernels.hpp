@@ -184,5 +184,19 @@ hipError_t launch_jacobian_wind(const ModelConst& P, int count, const double* x,
                                 double* J, hipStream_t s);
 // dst (B x 3) <- B winds `stride` doubles apart at src, clamped to +-wmax, non-finite -> 0
 hipError_t launch_wind_copy(int B, const double* src, int stride, double wmax, double* dst, hipStream_t s);
+// Kinematic (pose-only) EKF (kinekf_kernels.hip, model: kin_model.hpp):
+// `substeps` propagations of dt / substeps (+ one update when z != nullptr),
+// in place on x13 and Pc (count x 13 x 13); frame: the motion-capture -> world
+// change applied to a copy of z (host pointer, passed by value into the
+// launch), or nullptr: z is a world pose; status as launch_ekf_wind's
+struct PoseFrame;
+hipError_t launch_ekf_kin(int count, double dt, int substeps, double* x13, double* Pc, const double* z,
+                          const double* W, const double* V, const PoseFrame* frame, int32_t* status, hipStream_t s);
+// x13 (count x 13) from two world poses dt apart (KiteEKF_Node::initialize);
+// status: count words (nullable), KITE_EKF_INIT_BAD per kite, written on every call
+hipError_t launch_ekf_kin_init(int count, double dt, const double* prev7, const double* next7, const PoseFrame* frame,
+                               double* x13, int32_t* status, hipStream_t s);
+// J (count x 13 x 13) = df/dx of the kinematic model
+hipError_t launch_jacobian_kin(int count, const double* x, double* J, hipStream_t s);
 
 }  // namespace kite

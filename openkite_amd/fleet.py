@@ -10,6 +10,10 @@ One step of a fleet of kites on one rank:
          wind as three more states (kite_nmpc_windekf_step_device), the same
          propagation and update in one launch, after which the estimated wind
          becomes the wind of the RTI's model (kite_nmpc_set_wind_device).
+         With ``kin_ekf``: the kinematic, model-free filter of the reference's
+         estimator node (kite_nmpc_kinekf_step_device), one launch as well;
+         it uses no control and no aerodynamic constant, so a flight log
+         recorded from it is independent of every model row.
   RTI    one real-time iteration of the NMPC for every kite of the shard
          (kite_nmpc_step_device: KiteNMPF::computeControl, kiteNMPF.cpp:199-316).
   pub    optional publish of u0 + mpc_diagnostic of every kite to every rank
@@ -77,6 +81,13 @@ class GpuStepper:
         self.ctx.wind_ekf_step_device(xe.shape[0], dt, substeps, xe.data_ptr(), u3.data_ptr(), P.data_ptr(),
                                       z.data_ptr() if z is not None else 0, W.data_ptr(), V.data_ptr(),
                                       status.data_ptr() if status is not None else 0)
+
+    def kin_ekf(self, dt, substeps, xe, P, z, W, V, status, frame=None):
+        """One fused step of the kinematic EKF on xe (B, 13) and P (B, 13, 13);
+        frame: a ``PoseFrame`` when z holds motion-capture poses."""
+        self.ctx.kin_ekf_step_device(xe.shape[0], dt, substeps, xe.data_ptr(), P.data_ptr(),
+                                     z.data_ptr() if z is not None else 0, W.data_ptr(), V.data_ptr(),
+                                     status.data_ptr() if status is not None else 0, frame=frame)
 
     def set_wind_device(self, wind, wmax):
         """The controller's wind from a (B, 3) view of a device tensor (rows
@@ -226,11 +237,15 @@ class FleetLoop:
     def __init__(self, stepper, x0: torch.Tensor, N: int, dt: float, ekf: bool = False, ekf_substeps: int = 5,
                  covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None,
                  plant=None, wind_ekf: bool = False, wind_max: float = 20.0, recorder=None, adapt=None,
-                 estimator_model: str = "creation", ident_wind=None):
+                 estimator_model: str = "creation", ident_wind=None, kin_ekf: bool = False):
         if ekf and wind_ekf:
             raise ValueError("ekf and wind_ekf are two estimators: choose one")
+        if kin_ekf and (ekf or wind_ekf):
+            raise ValueError("kin_ekf, ekf and wind_ekf are three estimators: choose one")
         if estimator_model not in ("creation", "controller"):
             raise ValueError('estimator_model is "creation" or "controller"')
+        if estimator_model == "controller" and kin_ekf:
+            raise ValueError('estimator_model="controller" chooses a model: the kinematic filter has none')
         if estimator_model == "controller" and not (ekf or wind_ekf):
             raise ValueError('estimator_model="controller" needs an estimator: ekf=True or wind_ekf=True')
         if adapt is not None and recorder is None:
@@ -286,6 +301,23 @@ class FleetLoop:
             self.z = self.x0[:, 6:13].clone()
             self.ekf_status = torch.zeros((B,), dtype=torch.int32, device=dev)
             self.wind_ekf_fresh = True
+        # the kinematic EKF: xe = x13, P 13 x 13 with KiteEKF's covariances; one
+        # fused call per step, no control and no model
+        self.kin_ekf = kin_ekf
+        if kin_ekf:
+            if covariances is None:
+                raise ValueError("the kinematic EKF needs (W, V, P0)")
+            W, V, P0 = (np.asarray(a, dtype=np.float64) for a in covariances)
+            if W.shape != (13, 13) or V.shape != (7, 7) or P0.shape != (13, 13):
+                raise ValueError("the kinematic EKF needs W (13, 13), V (7, 7), P0 (13, 13)")
+            self.W = torch.from_numpy(W.copy()).to(dev)
+            self.V = torch.from_numpy(V.copy()).to(dev)
+            self.P = torch.from_numpy(np.repeat(P0[None], B, axis=0)).to(dev)
+            self.P_init = self.P.clone()
+            self.xe = self.x0[:, :13].clone().contiguous()
+            self.z = self.x0[:, 6:13].clone()
+            self.ekf_status = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self.kin_ekf_fresh = True
         # the estimator filters with the controller's models in force (per kite
         # once ``adapt`` or set_params_device has set them) instead of the
         # creation model; "creation" calls nothing
@@ -359,6 +391,12 @@ class FleetLoop:
             self.z.copy_(self.x_init[:, 6:13])
             self.ekf_status.zero_()
             self.wind_ekf_fresh = True
+        if self.kin_ekf:
+            self.xe.copy_(self.x_init[:, :13])
+            self.P.copy_(self.P_init)
+            self.z.copy_(self.x_init[:, 6:13])
+            self.ekf_status.zero_()
+            self.kin_ekf_fresh = True
 
     def _adapt(self):
         """The full log becomes the controller's models, on the stream with no
@@ -399,6 +437,16 @@ class FleetLoop:
                                       self.ekf_status)
             self.stepper.set_wind_device(self.xe[:, 13:], self.wind_max)
             self.x0[:, :13].copy_(self.xe[:, :13])
+        if self.kin_ekf:
+            # one launch: ekf_substeps propagations and the update.  The first
+            # step of an episode filters nothing, as with the wind EKF: xe is
+            # the state measured at this instant and no time has passed.
+            if self.kin_ekf_fresh:
+                self.kin_ekf_fresh = False
+            else:
+                self.stepper.kin_ekf(self.dt, self.ekf_substeps, self.xe, self.P, self.z, self.W, self.V,
+                                     self.ekf_status)
+            self.x0[:, :13].copy_(self.xe)
         if self.ekf:
             # propagate under the control applied last (u(t0) of the previous
             # plan), update with the measurement on the last substep
@@ -434,5 +482,5 @@ class FleetLoop:
             self.x0[:, 13:].copy_(self.traj[:, 1, 13:])
         if self.noise is not None:
             self.noise.apply(self.x0)
-        if self.ekf or self.wind_ekf:
+        if self.ekf or self.wind_ekf or self.kin_ekf:
             self.z.copy_(self.x0[:, 6:13])

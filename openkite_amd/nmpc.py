@@ -24,7 +24,8 @@ KITE_OK, KITE_EINVAL, KITE_EHIP, KITE_ENOMEM, KITE_ENODEV, KITE_EIO, KITE_EPARSE
 ST_NAN, ST_QP_NOT_CONV, ST_MIN_SPEED, ST_STATE_BOUND, ST_THETA_WRAP, ST_STEP_REJECTED = 1, 2, 4, 8, 16, 32
 ST_RESTART = 64
 PLANT_NAN = 1                      # KITE_PLANT_NAN (plant status word)
-EKF_NAN, EKF_S_NOT_PD = 1, 2       # KITE_EKF_* (status word of the wind-estimating EKF)
+EKF_NAN, EKF_S_NOT_PD = 1, 2       # KITE_EKF_* (status word of the wind-estimating and the kinematic EKF)
+EKF_INIT_BAD = 4                   # KITE_EKF_INIT_BAD (status word of kin_ekf_init)
 WIND_MAX_DEFAULT = 20.0            # set_wind_device: clamp of an estimated wind component, m/s
 IDENT_NAN, IDENT_CONVERGED, IDENT_AT_BOUND = 1, 2, 4   # KITE_IDENT_* (status word of the identification)
 PARAMS_REJECTED = 1                # KITE_PARAMS_REJECTED (status word of set_params_device)
@@ -138,6 +139,24 @@ class IdentConfig(ctypes.Structure):
         return d
 
 
+class PoseFrame(ctypes.Structure):
+    """kite_pose_frame: the motion-capture -> world change of a measured pose
+    (optitrack2world, ekf_node.cpp:148-169)."""
+    _fields_ = [("offset", ctypes.c_double * 3), ("rotation", ctypes.c_double * 4), ("shift", ctypes.c_double * 3)]
+
+    def to_dict(self) -> dict:
+        return {name: tuple(getattr(self, name)) for name, _ in self._fields_}
+
+
+def _frame(frame):
+    """A ``PoseFrame`` (or a dict of its three fields) as the C argument; None stays NULL."""
+    if frame is None:
+        return None
+    if not isinstance(frame, PoseFrame):
+        frame = PoseFrame(*(tuple(float(v) for v in frame[k]) for k in ("offset", "rotation", "shift")))
+    return ctypes.byref(frame)
+
+
 class MpcDiagnostic(ctypes.Structure):
     """msg/mpc_diagnostic.msg field order."""
     _fields_ = [("pos_error", ctypes.c_double), ("vel_error", ctypes.c_double), ("cost", ctypes.c_double),
@@ -206,6 +225,19 @@ _SIGNATURES = {
                                                      ctypes.c_void_p]),
     "kite_nmpc_jacobian_wind": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, _DP]),
     "kite_nmpc_set_wind_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double]),
+    "kite_pose_frame_default": (None, [ctypes.POINTER(PoseFrame)]),
+    "kite_nmpc_kinekf_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _DP,
+                                             _DP, _DP, _DP, _DP, ctypes.POINTER(PoseFrame), _IP]),
+    "kite_nmpc_kinekf_step_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(PoseFrame),
+                                                    ctypes.c_void_p]),
+    "kite_nmpc_kinekf_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, _DP, _DP,
+                                             ctypes.POINTER(PoseFrame), _DP, _IP]),
+    "kite_nmpc_kinekf_init_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(PoseFrame),
+                                                    ctypes.c_void_p, ctypes.c_void_p]),
+    "kite_nmpc_jacobian_kin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _DP, _DP]),
     "kite_nmpc_set_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "kite_nmpc_set_params_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "kite_nmpc_get_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -656,6 +688,69 @@ class BatchNMPC:
         _check(lib().kite_nmpc_set_wind_device(self._h, ctypes.c_void_p(ptr) if ptr else None, int(stride),
                                                float(wmax)), "set_wind_device")
 
+    # --- kinematic (pose-only) EKF ----------------------------------------------
+    def kin_ekf_step_device(self, count: int, dt: float, substeps: int, d_x13: int, d_P169: int, d_z7: int,
+                            d_W169: int, d_V49: int, d_status: int = 0, frame=None):
+        """Device-pointer step of the kinematic EKF (kite_nmpc_kinekf_step_device,
+        asynchronous on the context stream); frame: a ``PoseFrame`` on the
+        host, passed by value into the launch, or None."""
+        _check(lib().kite_nmpc_kinekf_step_device(self._h, int(count), float(dt), int(substeps), d_x13, d_P169,
+                                                  d_z7 or None, d_W169, d_V49 or None, _frame(frame),
+                                                  d_status or None), "kin_ekf_step_device")
+
+    def kin_ekf_step(self, x13, P, dt: float, substeps: int = 1, z7=None, W=None, V=None, frame=None):
+        """Batched kinematic EKF (kite_nmpc_kinekf_step): the model-free filter
+        of the reference's estimator node, P (count, 13, 13); `substeps`
+        propagations of dt / substeps, then one update when z7 is given.  frame
+        (a ``PoseFrame``): z7 are motion-capture poses and are moved to the world
+        frame first, on a copy; None: world poses.  Returns (x13, P, status),
+        status the KITE_EKF_* words (``EKF_NAN``, ``EKF_S_NOT_PD``)."""
+        x = _f64(x13).reshape(-1, 13).copy()
+        c = x.shape[0]
+        Pm = _f64(P).reshape(c, 13, 13).copy()
+        Wd, Vd, _ = ekf_default_covariances()
+        W = Wd if W is None else _f64(W).reshape(13, 13)
+        V = Vd if V is None else _f64(V).reshape(7, 7)
+        z = None if z7 is None else _f64(z7).reshape(c, 7)
+        st = np.zeros(c, dtype=np.int32)
+        _check(lib().kite_nmpc_kinekf_step(self._h, c, float(dt), int(substeps), _p(x), _p(Pm), _p(z), _p(W), _p(V),
+                                           _frame(frame), st.ctypes.data_as(_IP)), "kin_ekf_step")
+        return x, Pm, st
+
+    def kin_ekf_init_device(self, count: int, dt: float, d_prev7: int, d_new7: int, d_x13: int, d_status: int = 0,
+                            frame=None):
+        """Device-pointer form of ``kin_ekf_init`` (asynchronous on the context stream)."""
+        _check(lib().kite_nmpc_kinekf_init_device(self._h, int(count), float(dt), d_prev7, d_new7, _frame(frame),
+                                                  d_x13, d_status or None), "kin_ekf_init_device")
+
+    def kin_ekf_init(self, pose_prev, pose_new, dt: float, frame=None, x13=None):
+        """The 13 states from two consecutive poses (count, 7) dt apart
+        (kite_nmpc_kinekf_init: KiteEKF_Node::initialize).  Returns (x13,
+        status); a kite with ``EKF_INIT_BAD`` (dt <= 0 or non-finite, a
+        non-finite pose) keeps its row of the x13 passed in (zeros without)."""
+        mp = _f64(pose_prev).reshape(-1, 7); mn = _f64(pose_new).reshape(-1, 7)
+        c = mp.shape[0]
+        if mn.shape[0] != c:
+            raise ValueError("pose_prev and pose_new: one pose per kite each")
+        x = np.zeros((c, 13)) if x13 is None else _f64(x13).reshape(c, 13).copy()
+        st = np.zeros(c, dtype=np.int32)
+        _check(lib().kite_nmpc_kinekf_init(self._h, c, float(dt), _p(mp), _p(mn), _frame(frame), _p(x),
+                                           st.ctypes.data_as(_IP)), "kin_ekf_init")
+        return x, st
+
+    def jacobian_kin(self, x13):
+        """df/dx (count, 13, 13) of the kinematic model at x13: the kinematic
+        filter's Jacobian pass."""
+        x = _f64(x13).reshape(-1, 13)
+        J = np.zeros((x.shape[0], 13, 13))
+        _check(lib().kite_nmpc_jacobian_kin(self._h, x.shape[0], _p(x), _p(J)), "jacobian_kin")
+        return J
+
+    @staticmethod
+    def pose_frame_default() -> PoseFrame:
+        """The reference node's frame (kite_pose_frame_default)."""
+        return pose_frame_default()
+
     # --- per-kite controller models --------------------------------------------
     def set_params(self, rows=None):
         """The model of the step's predictions (kite_nmpc_set_params): None =
@@ -692,6 +787,7 @@ class BatchNMPC:
 
     def set_estimator_model(self, mode: int):
         """The model of ``ekf_step`` / ``wind_ekf_step`` and their device forms
+        (not of ``kin_ekf_step``, which has no model)
         (kite_nmpc_set_estimator_model): ``EST_MODEL_CREATION`` (the default) or
         ``EST_MODEL_CONTROLLER``, the controller's models in force at each call
         (``set_params[_device]``).  With a model per kite in force kite b
@@ -944,6 +1040,14 @@ def ekf_default_covariances():
     return W, V, P0
 
 
+def pose_frame_default() -> PoseFrame:
+    """The reference node's motion-capture -> world frame (kite_pose_frame_default):
+    offset (-0.09, 0, -0.02), rotation (0, -1, 0, 0), shift (0, 0, 2.77)."""
+    f = PoseFrame()
+    lib().kite_pose_frame_default(ctypes.byref(f))
+    return f
+
+
 def wind_ekf_default_covariances():
     """(W, V, P0) of the wind-estimating EKF, 16 x 16 / 7 x 7 / 16 x 16: the
     ``ekf_default_covariances`` blocks and the wind block of
@@ -958,11 +1062,25 @@ class KiteEKF:
     kites on one GPU context: same setters/getters, ``propagate(dt)`` and
     ``_estimate(measurement, dt)``; ``estimate(measurement, tstamp)`` takes
     dt = tstamp - getTimeStamp() and, as in the reference (kiteEKF.cpp:100-105),
-    leaves the time stamp to ``setTime``."""
+    leaves the time stamp to ``setTime``.
 
-    def __init__(self, batch: int = 1, params: Optional[KiteParams] = None, device: int = 0):
+    model="kite" (the default) mirrors ``KiteEKF(KiteProperties,
+    AlgorithmProperties)``: the filter with the kite's aerodynamic model.
+    model="kinematic" mirrors ``KiteEKF(Function, Function)`` as the reference's
+    estimator node builds it (ekf_node.cpp:235-241): the model-free filter of
+    ``BatchNMPC.kin_ekf_step`` with ``substeps`` propagations per call and an
+    optional pose ``frame``; ``setControl`` is accepted and ignored,
+    ``initialize`` is the node's two-pose initialisation and ``status`` holds
+    the KITE_EKF_* words of the last call."""
+
+    def __init__(self, batch: int = 1, params: Optional[KiteParams] = None, device: int = 0, model: str = "kite",
+                 substeps: int = 1, frame=None):
+        if model not in ("kite", "kinematic"):
+            raise ValueError('model is "kite" or "kinematic"')
         self._ctx = BatchNMPC(params if params is not None else load_properties(), default_config(device=device), batch)
         self.batch = batch
+        self.model, self.substeps, self.frame = model, int(substeps), frame
+        self.status = np.zeros(batch, dtype=np.int32)
         self.W, self.V, P0 = ekf_default_covariances()
         self.P = np.repeat(P0[None], batch, axis=0)
         self.x = np.zeros((batch, 13))
@@ -983,11 +1101,30 @@ class KiteEKF:
     def getTimeStamp(self): return self.tstamp
 
     def propagate(self, dt: float):
+        if self.model == "kinematic":
+            self.x, self.P, self.status = self._ctx.kin_ekf_step(self.x, self.P, dt, self.substeps, None, self.W,
+                                                                 self.V)
+            return
         self.x, self.P = self._ctx.ekf_step(self.x, self.u, self.P, dt, None, self.W, self.V)
 
     def _estimate(self, measurement, dt: float):
         z = np.broadcast_to(_f64(measurement).reshape(-1, 7), (self.batch, 7))
+        if self.model == "kinematic":
+            self.x, self.P, self.status = self._ctx.kin_ekf_step(self.x, self.P, dt, self.substeps, z, self.W,
+                                                                 self.V, self.frame)
+            return
         self.x, self.P = self._ctx.ekf_step(self.x, self.u, self.P, dt, z, self.W, self.V)
+
+    def initialize(self, pose_prev, pose_new, dt: float):
+        """KiteEKF_Node::initialize (ekf_node.cpp:68-132), model="kinematic":
+        the estimate from two consecutive poses dt apart, both through the
+        frame; a kite that cannot be initialised keeps its estimate and has
+        ``EKF_INIT_BAD`` in ``status``.  The time stamp is left to ``setTime``."""
+        if self.model != "kinematic":
+            raise ValueError('initialize belongs to KiteEKF(model="kinematic")')
+        mp = np.broadcast_to(_f64(pose_prev).reshape(-1, 7), (self.batch, 7))
+        mn = np.broadcast_to(_f64(pose_new).reshape(-1, 7), (self.batch, 7))
+        self.x, self.status = self._ctx.kin_ekf_init(mp, mn, dt, self.frame, self.x)
 
     def estimate(self, measurement, tstamp: float):
         self._estimate(measurement, tstamp - self.tstamp)
