@@ -62,7 +62,12 @@ extern "C" {
                                       _ident_normal_wind, _ident_sens_wind) and the
                                       kinematic EKF (kite_nmpc_kinekf_step[_device],
                                       _kinekf_init[_device], _jacobian_kin,
-                                      kite_pose_frame, KITE_EKF_INIT_BAD)         */
+                                      kite_pose_frame, KITE_EKF_INIT_BAD) and the
+                                      wind identified jointly with the 21
+                                      (kite_nmpc_identify_joint[_device],
+                                      _ident_normal_joint, _ident_sens_joint,
+                                      kite_ident_wind_config,
+                                      KITE_IDENT_WIND_AT_BOUND)                   */
 #define KITE_PATH_MAX_HARMONICS 8 /* Fourier path: harmonics per axis              */
 
 /* ---- error codes ------------------------------------------------------ */
@@ -664,6 +669,69 @@ int kite_nmpc_identify_wind_device(kite_nmpc_ctx* ctx, const kite_ident_config* 
                                    const double* d_params, int32_t nparams, const double* d_X, const double* d_U,
                                    const double* d_W, double* d_params_out, double* d_cost2, int32_t* d_evals,
                                    int32_t* d_status, double* d_workspace);
+/* ---- the wind identified jointly with the 21 (additive, no version change) ----
+ * For a fleet whose wind nobody knows: per kite and log, 24 unknowns.
+ *   unknowns   the 21 coefficients and a constant world-frame wind offset w (3)
+ *   model      the model of sample k sees the wind W0[k] + w (the logged-wind
+ *              model above).  W0 is an optional known log, count x T x 3, NULL =
+ *              zeros: NULL is "no idea of the wind", W0 = a logged estimate (the
+ *              wind EKF's) is "correct the bias of that estimate"
+ *   variables  z[0:21] as above; z[21:24] = (w - w_prior) / w_scale
+ *   cost       c = 1/T sum_k e_k' Q e_k + alpha |z[0:21]|^2 + alpha_w |z[21:24]|^2
+ *   normal eq. A = 1/T sum S~' Q S~ + diag(alpha I21, alpha_w I3),
+ *              g = 1/T sum S~' Q e - (alpha z[0:21], alpha_w z[21:24]),
+ *              S~ = (d x^_k / d (p, w)) diag(s, w_scale), 13 x 24
+ *   box        the 21 as above; |w_i - w_prior_i| <= w_box_i (+INFINITY = free)
+ * Segments, chunking (KITE_IDENT_CHUNK), the ordered atomics-free sums and the
+ * iteration rule are those of the 21: accept / reject, lambda /4 and x8, active
+ * set, Cholesky on the free set, clip, tol -- with 24 variables, and the damping
+ * lambda tr(A) / 24.  The iteration starts at the input row and w = w_prior.
+ * Status: the bits above keep their meaning (KITE_IDENT_AT_BOUND: one of the 21
+ * ends on its box); KITE_IDENT_WIND_AT_BOUND: a wind component ends on its box.
+ * A non-finite entry in W0, the log or the row makes that kite's cost
+ * non-finite, which is never accepted: the kite returns its input row and
+ * w_prior with KITE_IDENT_NAN, the others are not affected.
+ * Argument rules: those of the _wind entries; in addition w_scale <= 0 or
+ * non-finite, a negative or NaN w_box / alpha_w (alpha_w also non-finite), a
+ * non-finite w_prior, or a NULL wind config: KITE_EINVAL, nothing is launched. */
+#define KITE_IDENT_NPW       24  /* the 21 and the wind offset                       */
+#define KITE_IDENT_WIND_AT_BOUND 8
+typedef struct kite_ident_wind_config {
+    double w_scale;       /* scale of the wind variables [m/s] (1.0)                 */
+    double w_prior[3];    /* centre of the box, start of the iteration [m/s] (0)     */
+    double w_box[3];      /* half-width of the box [m/s] (3.0; +INFINITY: free)      */
+    double alpha_w;       /* weight of |z[21:24]|^2 (0)                              */
+} kite_ident_wind_config;
+void kite_ident_wind_default_config(kite_ident_wind_config* cfg);
+/* One sample interval per item under the wind w3 (count x 3, the total wind):
+ * x13_out and S = d x+ / d (p, w), count x 13 x 24, unscaled.                 */
+int kite_nmpc_ident_sens_joint(kite_nmpc_ctx* ctx, int32_t count, double h, int32_t substeps,
+                               const kite_params* params, int32_t nparams, const double* x13, const double* u3,
+                               const double* w3, double* x13_out, double* S);
+/* One evaluation at p21 (count x 21) and the wind offset w3 (count x 3): A
+ * (count x 24 x 24, full, exactly symmetric), g (count x 24), cost (count);
+ * W0 count x T x 3 or NULL.  iters, lm0, tol and the boxes are not used.      */
+int kite_nmpc_ident_normal_joint(kite_nmpc_ctx* ctx, const kite_ident_config* cfg,
+                                 const kite_ident_wind_config* wcfg, int32_t count, int32_t T,
+                                 const kite_params* params, int32_t nparams, const double* p21, const double* w3,
+                                 const double* X, const double* U, const double* W0, double* A, double* g,
+                                 double* cost, int32_t* status);
+/* The joint identification.  params_out count x 52, wind_out count x 3 (the
+ * identified offset w; the model's wind is W0 + w), cost2, evals, status as
+ * kite_nmpc_identify.                                                          */
+int kite_nmpc_identify_joint(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, const kite_ident_wind_config* wcfg,
+                             int32_t count, int32_t T, const kite_params* params, int32_t nparams, const double* X,
+                             const double* U, const double* W0, kite_params* params_out, double* wind_out,
+                             double* cost2, int32_t* evals, int32_t* status);
+/* Same on device pointers with a workspace of
+ * kite_nmpc_ident_joint_workspace_doubles doubles: 2 * iters launches on the
+ * context stream, no allocation, no copy, no synchronisation.  d_W0 nullable. */
+int kite_nmpc_identify_joint_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg,
+                                    const kite_ident_wind_config* wcfg, int32_t count, int32_t T,
+                                    const double* d_params, int32_t nparams, const double* d_X, const double* d_U,
+                                    const double* d_W0, double* d_params_out, double* d_wind_out, double* d_cost2,
+                                    int32_t* d_evals, int32_t* d_status, double* d_workspace);
+int64_t kite_nmpc_ident_joint_workspace_doubles(const kite_ident_config* cfg, int32_t count, int32_t T);
 
 /* Per-kernel device time [ms] of the last step (cfg.timing = 1):
  * [prologue, rk4_sens, condense, qp, total, qp_main]; qp is the whole QP

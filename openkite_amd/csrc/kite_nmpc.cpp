@@ -1734,6 +1734,161 @@ int kite_nmpc_identify(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, int32_t
                                    status);
 }
 
+// ---- the wind identified jointly with the 21 (k_ident_accum_jw, k_ident_solve24) ----
+void kite_ident_wind_default_config(kite_ident_wind_config* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->w_scale = 1.0;
+    for (int i = 0; i < 3; ++i) c->w_box[i] = 3.0;
+}
+
+extern "C++" {
+namespace {
+int make_ident_wind_const(const kite_ident_wind_config* w, kite::IdentWindConst* out) {
+    if (!w) return KITE_EINVAL;
+    if (!std::isfinite(w->w_scale) || !(w->w_scale > 0.0)) return KITE_EINVAL;
+    if (!std::isfinite(w->alpha_w) || !(w->alpha_w >= 0.0)) return KITE_EINVAL;
+    kite::IdentWindConst k;
+    k.w_scale = w->w_scale; k.alpha_w = w->alpha_w;
+    for (int i = 0; i < 3; ++i) {
+        if (!(w->w_box[i] >= 0.0) || !std::isfinite(w->w_prior[i])) return KITE_EINVAL;     // +INFINITY: free
+        k.w_box[i] = w->w_box[i]; k.w_prior[i] = w->w_prior[i];
+    }
+    *out = k;
+    return KITE_OK;
+}
+
+int ident_joint_run_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, const kite::IdentConst& K,
+                           const kite::IdentWindConst& WK, const double* d_rows, const double* d_X, const double* d_U,
+                           const double* d_W0, double* d_out, double* d_wind, double* d_cost2, int32_t* d_evals,
+                           int32_t* d_status, double* ws) {
+    double* state = ws;
+    double* slab = ws + (size_t)K.count * kite::IDJ_STATE;
+    hipStream_t s = ctx->stream;
+    for (int it = 0; it < cfg->iters; ++it) {
+        const int first = it == 0;
+        HIP_TRY(kite::launch_ident_accum_jw(K, WK, d_rows, first ? nullptr : state + kite::IDJ_S_PT,
+                                            first ? nullptr : state + kite::IDJ_S_PT + KITE_IDENT_NP, kite::IDJ_STATE,
+                                            kite::IDJ_STATE,
+                                            first ? nullptr : state, d_X, d_U, d_W0, slab, s));
+        HIP_TRY(kite::launch_ident_solve24(K, WK, first, 0, d_rows, nullptr, nullptr, slab, state, nullptr, nullptr,
+                                           nullptr, d_out, d_wind, d_cost2, d_evals, d_status, s));
+    }
+    return KITE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int64_t kite_nmpc_ident_joint_workspace_doubles(const kite_ident_config* cfg, int32_t count, int32_t T) {
+    kite::IdentConst K;
+    const int rc = make_ident_const(cfg, count, T, 1, &K);
+    if (rc) return rc;
+    return (int64_t)count * kite::IDJ_STATE + (int64_t)count * K.nchunks * kite::IDJ_SLAB;
+}
+
+int kite_nmpc_ident_sens_joint(kite_nmpc_ctx* ctx, int32_t count, double h, int32_t substeps,
+                               const kite_params* params, int32_t nparams, const double* x13, const double* u3,
+                               const double* w3, double* x13_out, double* S) {
+    if (!ctx || count < 1 || !x13 || !u3 || !w3 || !x13_out || !S || (nparams != 1 && nparams != count))
+        return KITE_EINVAL;
+    if (!std::isfinite(h) || !(h > 0.0) || substeps < 1 || substeps > 64) return KITE_EINVAL;
+    const int rc = ident_rows_ok(params, nparams, false);
+    if (rc) return rc;
+    const size_t c = count;
+    return run_items(ctx,
+                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {x13, c * 13}, {u3, c * 3},
+                      {w3, c * 3}},
+                     {{x13_out, c * 13}, {S, c * 13 * KITE_IDENT_NPW}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         return kite::launch_ident_sens_jw(count, nparams, h / substeps, substeps, i[0], i[1], i[2],
+                                                           i[3], o[0], o[1], s);
+                     });
+}
+
+int kite_nmpc_ident_normal_joint(kite_nmpc_ctx* ctx, const kite_ident_config* cfg,
+                                 const kite_ident_wind_config* wcfg, int32_t count, int32_t T,
+                                 const kite_params* params, int32_t nparams, const double* p21, const double* w3,
+                                 const double* X, const double* U, const double* W0, double* A, double* g,
+                                 double* cost, int32_t* status) {
+    if (!ctx || !p21 || !w3 || !X || !U || !A || !g || !cost) return KITE_EINVAL;
+    kite::IdentConst K;
+    kite::IdentWindConst WK;
+    int rc = make_ident_const(cfg, count, T, nparams, &K);
+    if (rc) return rc;
+    rc = make_ident_wind_const(wcfg, &WK);
+    if (rc) return rc;
+    rc = ident_rows_ok(params, nparams, true);
+    if (rc) return rc;
+    const size_t c = count, NJ = KITE_IDENT_NPW;
+    return run_items(ctx,
+                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {p21, c * KITE_IDENT_NP},
+                      {w3, c * 3}, {X, c * (T + 1) * 13}, {U, c * T * 3}, {W0, W0 ? c * T * 3 : 0}},
+                     {{A, c * NJ * NJ}, {g, c * NJ}, {cost, c}, {nullptr, (c + 1) / 2},
+                      {nullptr, c * K.nchunks * kite::IDJ_SLAB}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         int32_t* dst = reinterpret_cast<int32_t*>(o[3]);
+                         hipError_t e = kite::launch_ident_accum_jw(K, WK, i[0], i[1], i[2], KITE_IDENT_NP, 3, nullptr, i[3], i[4],
+                                                                    W0 ? i[5] : nullptr, o[4], s);
+                         if (e != hipSuccess) return e;
+                         e = kite::launch_ident_solve24(K, WK, 0, 1, i[0], i[1], i[2], o[4], nullptr, o[0], o[1], o[2],
+                                                        nullptr, nullptr, nullptr, nullptr, dst, s);
+                         if (e != hipSuccess || !status) return e;
+                         return hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+                     });
+}
+
+int kite_nmpc_identify_joint_device(kite_nmpc_ctx* ctx, const kite_ident_config* cfg,
+                                    const kite_ident_wind_config* wcfg, int32_t count, int32_t T,
+                                    const double* d_params, int32_t nparams, const double* d_X, const double* d_U,
+                                    const double* d_W0, double* d_params_out, double* d_wind_out, double* d_cost2,
+                                    int32_t* d_evals, int32_t* d_status, double* d_workspace) {
+    if (!ctx || !d_params || !d_X || !d_U || !d_params_out || !d_wind_out || !d_workspace) return KITE_EINVAL;
+    kite::IdentConst K;
+    kite::IdentWindConst WK;
+    int rc = make_ident_const(cfg, count, T, nparams, &K);
+    if (rc) return rc;
+    rc = make_ident_wind_const(wcfg, &WK);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return ident_joint_run_device(ctx, cfg, K, WK, d_params, d_X, d_U, d_W0, d_params_out, d_wind_out, d_cost2,
+                                  d_evals, d_status, d_workspace);
+}
+
+int kite_nmpc_identify_joint(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, const kite_ident_wind_config* wcfg,
+                             int32_t count, int32_t T, const kite_params* params, int32_t nparams, const double* X,
+                             const double* U, const double* W0, kite_params* params_out, double* wind_out,
+                             double* cost2, int32_t* evals, int32_t* status) {
+    if (!ctx || !X || !U || !params_out || !wind_out) return KITE_EINVAL;
+    kite::IdentConst K;
+    kite::IdentWindConst WK;
+    int rc = make_ident_const(cfg, count, T, nparams, &K);
+    if (rc) return rc;
+    rc = make_ident_wind_const(wcfg, &WK);
+    if (rc) return rc;
+    rc = ident_rows_ok(params, nparams, true);
+    if (rc) return rc;
+    const size_t c = count;
+    const size_t ws = (size_t)kite_nmpc_ident_joint_workspace_doubles(cfg, count, T);
+    return run_items(ctx,
+                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {X, c * (T + 1) * 13},
+                      {U, c * T * 3}, {W0, W0 ? c * T * 3 : 0}},
+                     {{reinterpret_cast<double*>(params_out), c * 52}, {wind_out, c * 3}, {cost2, 2 * c}, {nullptr, c},
+                      {nullptr, ws}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         int32_t* dev = reinterpret_cast<int32_t*>(o[3]);
+                         int32_t* dst = dev + c;
+                         if (ident_joint_run_device(ctx, cfg, K, WK, i[0], i[1], i[2], W0 ? i[3] : nullptr, o[0], o[1],
+                                                    o[2], dev, dst, o[4]) != KITE_OK)
+                             return hipErrorLaunchFailure;
+                         if (evals) {
+                             hipError_t e = hipMemcpyAsync(evals, dev, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+                             if (e != hipSuccess) return e;
+                         }
+                         if (status) return hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+                         return hipSuccess;
+                     });
+}
+
 int kite_nmpc_rk4_sens(kite_nmpc_ctx* ctx, int32_t count, const double* x15, const double* u4, double tf,
                        int32_t M, double* xnext, double* A, double* Bm) {
     if (!ctx || count < 1 || !x15 || !u4 || !xnext || !A || !Bm || M < 1 || !std::isfinite(tf)) return KITE_EINVAL;

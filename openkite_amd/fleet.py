@@ -117,6 +117,15 @@ class GpuStepper:
                                  out.data_ptr(), cost2.data_ptr(), evals.data_ptr(), status.data_ptr(), ws.data_ptr(),
                                  wind=W.data_ptr() if W is not None else 0)
 
+    def identify_joint(self, config, wind_config, T, rows, X, U, out, wind_out, cost2, evals, status, ws, W0=None):
+        """kite_nmpc_identify_joint_device on device tensors, a row per kite: the
+        21 and a constant wind offset (wind_out (B, 3)); W0: a known wind log
+        (B, T, 3) the offset is added to, None: zeros."""
+        self.ctx.identify_joint_device(config, wind_config, rows.shape[0], T, rows.data_ptr(), rows.shape[0],
+                                       X.data_ptr(), U.data_ptr(), out.data_ptr(), wind_out.data_ptr(),
+                                       cost2.data_ptr(), evals.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                       wind0=W0.data_ptr() if W0 is not None else 0)
+
 
 class GpuPlant:
     """The batched plant simulator of one C-ABI context on device tensors
@@ -237,7 +246,8 @@ class FleetLoop:
     def __init__(self, stepper, x0: torch.Tensor, N: int, dt: float, ekf: bool = False, ekf_substeps: int = 5,
                  covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None,
                  plant=None, wind_ekf: bool = False, wind_max: float = 20.0, recorder=None, adapt=None,
-                 estimator_model: str = "creation", ident_wind=None, kin_ekf: bool = False):
+                 estimator_model: str = "creation", ident_wind=None, kin_ekf: bool = False,
+                 ident_wind_config=None):
         if ekf and wind_ekf:
             raise ValueError("ekf and wind_ekf are two estimators: choose one")
         if kin_ekf and (ekf or wind_ekf):
@@ -250,12 +260,15 @@ class FleetLoop:
             raise ValueError('estimator_model="controller" needs an estimator: ekf=True or wind_ekf=True')
         if adapt is not None and recorder is None:
             raise ValueError("adapt identifies from a flight log: give the loop a recorder")
-        if isinstance(ident_wind, str):
+        joint = isinstance(ident_wind, str) and ident_wind == "joint"
+        if isinstance(ident_wind, str) and not joint:
             if ident_wind != "estimate":
-                raise ValueError('ident_wind is None, a (B, 3) tensor or "estimate"')
+                raise ValueError('ident_wind is None, a (B, 3) tensor, "estimate" or "joint"')
             if not wind_ekf:
                 raise ValueError('ident_wind="estimate" logs the wind EKF\'s estimate: it needs wind_ekf=True')
-        if ident_wind is not None and (recorder is None or getattr(recorder, "W", None) is None):
+        if joint and adapt is None:
+            raise ValueError('ident_wind="joint" identifies the wind with the 21: it needs adapt (and a recorder)')
+        if ident_wind is not None and not joint and (recorder is None or getattr(recorder, "W", None) is None):
             raise ValueError("ident_wind is logged by the recorder: give the loop a FlightRecorder(..., wind=True)")
         B = x0.shape[0]
         dev = x0.device
@@ -339,7 +352,9 @@ class FleetLoop:
         # wind in force for the controller this period, which is the wind EKF's
         # estimate as kite_nmpc_set_wind_device treats it (a non-finite
         # component 0, each clamped to +-wind_max)
+        # "joint": no wind is known; ``adapt`` identifies a constant wind with the 21
         self.ident_wind = ident_wind
+        self.ident_joint = joint
         if ident_wind is not None and not isinstance(ident_wind, str):
             if tuple(ident_wind.shape) != (B, 3):
                 raise ValueError(f"ident_wind: a (B, 3) = ({B}, 3) tensor, got {tuple(ident_wind.shape)}")
@@ -355,7 +370,17 @@ class FleetLoop:
             self.ident_evals = torch.zeros((B,), **i32)
             self.ident_status = torch.zeros((B,), **i32)       # KITE_IDENT_* of the last identification
             self.params_status = torch.zeros((B,), **i32)      # KITE_PARAMS_* of the last set_params_device
-            self._ident_ws = torch.empty((nmpc.ident_workspace_doubles(adapt, B, recorder.T),), **f64)
+            # "joint": the wind is identified with the 21 (a constant offset per kite
+            # on top of the recorder's wind log, zeros without one); no wind EKF and
+            # no wind log is needed.  ident_wind_est holds the last identified offset
+            if joint:
+                self.ident_wind_config = (ident_wind_config if ident_wind_config is not None
+                                          else nmpc.ident_wind_default_config())
+                self.ident_wind_est = torch.zeros((B, 3), **f64)
+                self._ident_wind_out = torch.zeros((B, 3), **f64)
+                self._ident_ws = torch.empty((nmpc.ident_joint_workspace_doubles(adapt, B, recorder.T),), **f64)
+            else:
+                self._ident_ws = torch.empty((nmpc.ident_workspace_doubles(adapt, B, recorder.T),), **f64)
             self._ident_ok = nmpc.IDENT_CONVERGED, nmpc.IDENT_NAN
         # a plant of its own (``GpuPlant``, or any object with h, steps and
         # advance): the loop carries the true kite state xp and the time t
@@ -375,7 +400,7 @@ class FleetLoop:
         self.x0.copy_(self.x_init)
         self.u0.zero_()
         if self.adapt is not None:
-            self.recorder.reset()      # a log does not span episodes; the adapted models stay
+            self.recorder.reset()      # a log does not span episodes; the adapted models (and wind) stay
         if self.plant is not None:
             self.xp.copy_(self.x_init[:, :13])
             self.t = 0.0
@@ -406,7 +431,11 @@ class FleetLoop:
         rejected there, ``params_status``); the log starts again with the state
         at hand.  This step's RTI already predicts with the new models."""
         rec = self.recorder
-        if getattr(rec, "W", None) is not None:
+        if self.ident_joint:
+            self.stepper.identify_joint(self.adapt, self.ident_wind_config, rec.T, self.model_rows, rec.X, rec.U,
+                                        self.ident_rows, self._ident_wind_out, self.ident_cost2, self.ident_evals,
+                                        self.ident_status, self._ident_ws, W0=getattr(rec, "W", None))
+        elif getattr(rec, "W", None) is not None:
             self.stepper.identify(self.adapt, rec.T, self.model_rows, rec.X, rec.U, self.ident_rows, self.ident_cost2,
                                   self.ident_evals, self.ident_status, self._ident_ws, W=rec.W)
         else:
@@ -416,6 +445,13 @@ class FleetLoop:
         ok = ((self.ident_status & conv) != 0) & ((self.ident_status & nan) == 0)
         self.model_rows.copy_(torch.where(ok[:, None], self.ident_rows, self.model_rows))
         self.stepper.set_params_device(self.model_rows, self.params_status)
+        if self.ident_joint:
+            # a kite whose fit did not converge keeps the wind it had; without a wind
+            # EKF nobody else tells the controller the wind
+            self.ident_wind_est.copy_(torch.where(ok[:, None], self._ident_wind_out, self.ident_wind_est))
+            if not self.wind_ekf:
+                self.ident_wind_est.clamp_(-self.wind_max, self.wind_max)
+                self.stepper.set_wind_device(self.ident_wind_est, self.wind_max)
         self.adapt_count += 1
         rec.reset()
         rec.record_state(self.x0)
@@ -462,7 +498,13 @@ class FleetLoop:
                 self._adapt()
         self.stepper.rti(self.x0, self.u0, self.traj, self.diag, self.status)
         if self.recorder is not None:
-            if self.ident_wind is not None:
+            if self.ident_joint:
+                # the known part W0 of the joint model's wind: the wind EKF's estimate
+                # where the loop runs one and the recorder logs a wind, else untouched
+                if self.wind_ekf and getattr(self.recorder, "W", None) is not None:
+                    w = torch.nan_to_num(self.xe[:, 13:16], nan=0.0, posinf=0.0, neginf=0.0)
+                    self.recorder.record_wind(w.clamp(-self.wind_max, self.wind_max))
+            elif self.ident_wind is not None:
                 if isinstance(self.ident_wind, str):
                     w = torch.nan_to_num(self.xe[:, 13:16], nan=0.0, posinf=0.0, neginf=0.0)
                     self.recorder.record_wind(w.clamp(-self.wind_max, self.wind_max))

@@ -28,6 +28,8 @@ EKF_NAN, EKF_S_NOT_PD = 1, 2       # KITE_EKF_* (status word of the wind-estimat
 EKF_INIT_BAD = 4                   # KITE_EKF_INIT_BAD (status word of kin_ekf_init)
 WIND_MAX_DEFAULT = 20.0            # set_wind_device: clamp of an estimated wind component, m/s
 IDENT_NAN, IDENT_CONVERGED, IDENT_AT_BOUND = 1, 2, 4   # KITE_IDENT_* (status word of the identification)
+IDENT_WIND_AT_BOUND = 8            # KITE_IDENT_WIND_AT_BOUND (joint identification: the wind ends on its box)
+IDENT_NPW = 24                     # KITE_IDENT_NPW: the 21 and the wind offset
 PARAMS_REJECTED = 1                # KITE_PARAMS_REJECTED (status word of set_params_device)
 EST_MODEL_CREATION = 0             # KITE_EST_MODEL_*: the model of the two EKFs (set_estimator_model)
 EST_MODEL_CONTROLLER = 1
@@ -130,6 +132,19 @@ class IdentConfig(ctypes.Structure):
         ("h", ctypes.c_double), ("Q", ctypes.c_double * 13), ("alpha", ctypes.c_double), ("lm0", ctypes.c_double),
         ("tol", ctypes.c_double), ("lb_rel", ctypes.c_double * 21), ("ub_rel", ctypes.c_double * 21),
     ]
+
+    def to_dict(self) -> dict:
+        d = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            d[name] = list(v) if hasattr(v, "__len__") else v
+        return d
+
+
+class IdentWindConfig(ctypes.Structure):
+    """kite_ident_wind_config: the wind variables of the joint identification."""
+    _fields_ = [("w_scale", ctypes.c_double), ("w_prior", ctypes.c_double * 3), ("w_box", ctypes.c_double * 3),
+                ("alpha_w", ctypes.c_double)]
 
     def to_dict(self) -> dict:
         d = {}
@@ -271,6 +286,25 @@ _SIGNATURES = {
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_void_p]),
+    "kite_ident_wind_default_config": (None, [ctypes.POINTER(IdentWindConfig)]),
+    "kite_nmpc_ident_sens_joint": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+                                                  ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, _DP, _DP]),
+    "kite_nmpc_ident_normal_joint": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IdentConfig),
+                                                    ctypes.POINTER(IdentWindConfig), ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, _DP, _DP, _DP, _DP,
+                                                    _DP, _IP]),
+    "kite_nmpc_identify_joint": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IdentConfig),
+                                                ctypes.POINTER(IdentWindConfig), ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP, ctypes.c_void_p, _DP,
+                                                _DP, _IP, _IP]),
+    "kite_nmpc_identify_joint_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IdentConfig),
+                                                       ctypes.POINTER(IdentWindConfig), ctypes.c_int32, ctypes.c_int32,
+                                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "kite_nmpc_ident_joint_workspace_doubles": (ctypes.c_int64, [ctypes.POINTER(IdentConfig), ctypes.c_int32,
+                                                                 ctypes.c_int32]),
     "kite_nmpc_plant_set_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "kite_nmpc_plant_set_wind": (ctypes.c_int, [ctypes.c_void_p, _DP]),
     "kite_nmpc_plant_step": (ctypes.c_int, [ctypes.c_void_p, _DP, _DP, ctypes.c_double, ctypes.c_double,
@@ -443,6 +477,29 @@ def ident_workspace_doubles(config: IdentConfig, count: int, T: int) -> int:
                   "ident_workspace_doubles")
 
 
+def ident_wind_default_config(**overrides) -> IdentWindConfig:
+    """kite_ident_wind_default_config: w_scale 1 m/s, prior 0, box +-3 m/s, no prior weight."""
+    c = IdentWindConfig()
+    lib().kite_ident_wind_default_config(ctypes.byref(c))
+    for k, v in overrides.items():
+        if not hasattr(c, k):
+            raise KeyError(k)
+        cur = getattr(c, k)
+        if hasattr(cur, "__len__"):
+            vv = np.broadcast_to(np.asarray(v, dtype=np.float64), (len(cur),))
+            for i, vi in enumerate(vv):
+                cur[i] = vi
+        else:
+            setattr(c, k, v)
+    return c
+
+
+def ident_joint_workspace_doubles(config: IdentConfig, count: int, T: int) -> int:
+    """Workspace of ``BatchNMPC.identify_joint_device`` in doubles."""
+    return _check(int(lib().kite_nmpc_ident_joint_workspace_doubles(ctypes.byref(config), int(count), int(T))),
+                  "ident_joint_workspace_doubles")
+
+
 @dataclass
 class IdentResult:
     """``BatchNMPC.identify``: params (B, 52) the input rows with the 21
@@ -453,6 +510,7 @@ class IdentResult:
     cost: np.ndarray
     evals: np.ndarray
     status: np.ndarray
+    wind: Optional[np.ndarray] = None      # identify_joint: (B, 3) the identified wind offset w
 
 
 class BatchNMPC:
@@ -985,6 +1043,83 @@ class BatchNMPC:
         _check(lib().kite_nmpc_identify_device(self._h, ctypes.byref(config), int(count), int(T), v(params_ptr),
                                                int(nparams), v(X_ptr), v(U_ptr), v(params_out_ptr), v(cost2_ptr),
                                                v(evals_ptr), v(status_ptr), v(workspace_ptr)), "identify_device")
+
+    # --- the wind identified jointly with the 21 --------------------------------
+    def ident_sens_joint(self, x13, u3, wind, h: float, substeps: int = 4, params=None):
+        """One sample interval per item under the wind (count, 3)
+        (kite_nmpc_ident_sens_joint): x+ (count, 13) and S = d x+ / d (p, w)
+        (count, 13, 24, unscaled): columns 0..20 ``IDENT_FIELDS``, 21..23 the wind."""
+        x = _f64(x13).reshape(-1, 13); u = _f64(u3).reshape(-1, 3)
+        c = x.shape[0]
+        p = self._ident_rows(params, c)
+        w = self._ident_wind(wind, c, None)
+        xo = np.zeros((c, 13)); S = np.zeros((c, 13, IDENT_NPW))
+        _check(lib().kite_nmpc_ident_sens_joint(self._h, c, float(h), int(substeps), ctypes.c_void_p(p.ctypes.data),
+                                                p.shape[0], _p(x), _p(u), _p(w), _p(xo), _p(S)), "ident_sens_joint")
+        return xo, S
+
+    def _joint_logs(self, X, U, wind0):
+        X = _f64(X); U = _f64(U)
+        B, T = U.shape[0], U.shape[1]
+        if X.shape != (B, T + 1, 13) or U.shape != (B, T, 3):
+            raise ValueError("logs: X (B, T+1, 13), U (B, T, 3)")
+        return X, U, B, T, (self._ident_wind(wind0, B, T) if wind0 is not None else None)
+
+    def ident_normal_joint(self, X, U, p21, w3, params=None, config: Optional[IdentConfig] = None,
+                           wind_config: Optional[IdentWindConfig] = None, wind0=None):
+        """One evaluation of the joint normal equations at the parameter values
+        p21 (B, 21) and the wind offset w3 (B, 3) (kite_nmpc_ident_normal_joint):
+        (A (B, 24, 24), g (B, 24), cost (B,), status (B,)) in the scaled variables.
+        wind0: the known wind log W0 (B, T, 3) or (B, 3), None: zeros; the model
+        of sample k sees W0[k] + w."""
+        cfg = config if config is not None else ident_default_config()
+        wc = wind_config if wind_config is not None else ident_wind_default_config()
+        X, U, B, T, W0 = self._joint_logs(X, U, wind0)
+        p = self._ident_rows(params, B)
+        q = _f64(p21).reshape(B, IDENT_NP)
+        w = self._ident_wind(w3, B, None)
+        A = np.zeros((B, IDENT_NPW, IDENT_NPW)); g = np.zeros((B, IDENT_NPW)); cost = np.zeros(B)
+        st = np.zeros(B, dtype=np.int32)
+        _check(lib().kite_nmpc_ident_normal_joint(self._h, ctypes.byref(cfg), ctypes.byref(wc), B, T,
+                                                  ctypes.c_void_p(p.ctypes.data), p.shape[0], _p(q), _p(w), _p(X),
+                                                  _p(U), _p(W0) if W0 is not None else None, _p(A), _p(g), _p(cost),
+                                                  st.ctypes.data_as(_IP)), "ident_normal_joint")
+        return A, g, cost, st
+
+    def identify_joint(self, X, U, params=None, config: Optional[IdentConfig] = None,
+                       wind_config: Optional[IdentWindConfig] = None, wind0=None) -> IdentResult:
+        """Fit the 21 coefficients and a constant world-frame wind offset w of
+        every kite to its log (kite_nmpc_identify_joint): for a fleet whose wind
+        nobody knows.  wind0: a known wind log W0 (B, T, 3) or (B, 3) the offset
+        is added to (a logged estimate whose bias is to be corrected), None:
+        zeros.  Returns the ``IdentResult`` with ``wind`` (B, 3), the identified w."""
+        cfg = config if config is not None else ident_default_config()
+        wc = wind_config if wind_config is not None else ident_wind_default_config()
+        X, U, B, T, W0 = self._joint_logs(X, U, wind0)
+        p = self._ident_rows(params, B)
+        out = np.zeros((B, len(_PARAM_FIELDS))); c2 = np.zeros((B, 2)); wo = np.zeros((B, 3))
+        ev = np.zeros(B, dtype=np.int32); st = np.zeros(B, dtype=np.int32)
+        _check(lib().kite_nmpc_identify_joint(self._h, ctypes.byref(cfg), ctypes.byref(wc), B, T,
+                                              ctypes.c_void_p(p.ctypes.data), p.shape[0], _p(X), _p(U),
+                                              _p(W0) if W0 is not None else None, ctypes.c_void_p(out.ctypes.data),
+                                              _p(wo), _p(c2), ev.ctypes.data_as(_IP), st.ctypes.data_as(_IP)),
+               "identify_joint")
+        return IdentResult(out, c2[:, 0].copy(), c2[:, 1].copy(), ev, st, wo)
+
+    def identify_joint_device(self, config: IdentConfig, wind_config: IdentWindConfig, count: int, T: int,
+                              params_ptr: int, nparams: int, X_ptr: int, U_ptr: int, params_out_ptr: int,
+                              wind_out_ptr: int, cost2_ptr: int = 0, evals_ptr: int = 0, status_ptr: int = 0,
+                              workspace_ptr: int = 0, wind0: int = 0):
+        """identify_joint on device pointers (kite_nmpc_identify_joint_device):
+        2 * iters launches on the context stream, nothing allocated, copied or
+        awaited; the workspace holds ``ident_joint_workspace_doubles`` doubles.
+        wind0: device pointer of the known wind log (count, T, 3), 0: zeros."""
+        v = lambda p: ctypes.c_void_p(p) if p else None
+        _check(lib().kite_nmpc_identify_joint_device(self._h, ctypes.byref(config), ctypes.byref(wind_config),
+                                                     int(count), int(T), v(params_ptr), int(nparams), v(X_ptr),
+                                                     v(U_ptr), v(wind0), v(params_out_ptr), v(wind_out_ptr),
+                                                     v(cost2_ptr), v(evals_ptr), v(status_ptr), v(workspace_ptr)),
+               "identify_joint_device")
 
     def rk4_sens(self, x15, u4, tf: float, M: int):
         x = _f64(x15).reshape(-1, 15); u = _f64(u4).reshape(-1, 4)
