@@ -12,24 +12,33 @@
     for (int i = 0; i < NK; ++i) x[i] = DT(ST(xk[i]), d0 == i ? one : zero, d1 == i ? one : zero);
 #pragma unroll
     for (int j = 0; j < NKU; ++j) u[j] = DT(ST(uk[j]), d0 == NK + j ? one : zero, d1 == NK + j ? one : zero);
+    // The RK4 stages are peeled at both ends: stage 0 evaluates the right-hand
+    // side on x itself (no xs = x, acc = x copies), stage 3 forms no next-stage
+    // state (nothing reads it).  The two middle stages stay one rolled loop.
+    // Operands and their order are those of the four-stage loop: same bits.
+    const ST w6 = hs / ST(6), w3 = hs / ST(3), hh = ST(0.5) * hs;
 #pragma unroll 1
     for (int m = 0; m < M; ++m) {
         DT xs[NK], acc[NK], kv[NK];
+        kite_rhs<DT, WIND>(P, x, u, kv, WIND ? wind + 3 * b : nullptr);
 #pragma unroll
-        for (int i = 0; i < NK; ++i) { xs[i] = x[i]; acc[i] = x[i]; }
+        for (int i = 0; i < NK; ++i) {
+            acc[i] = rk_axpy<DT, ST>(w6, kv[i], x[i]);
+            xs[i] = rk_axpy<DT, ST>(hh, kv[i], x[i]);
+        }
 #pragma unroll 1
-        for (int st = 0; st < 4; ++st) {
+        for (int st = 1; st < 3; ++st) {
             kite_rhs<DT, WIND>(P, xs, u, kv, WIND ? wind + 3 * b : nullptr);
-            const ST wa = (st == 0 || st == 3) ? hs / ST(6) : hs / ST(3);
-            const ST wn = (st < 2) ? ST(0.5) * hs : hs;
+            const ST wn = (st < 2) ? hh : hs;
 #pragma unroll
             for (int i = 0; i < NK; ++i) {
-                acc[i] = rk_axpy<DT, ST>(wa, kv[i], acc[i]);
+                acc[i] = rk_axpy<DT, ST>(w3, kv[i], acc[i]);
                 xs[i] = rk_axpy<DT, ST>(wn, kv[i], x[i]);
             }
         }
+        kite_rhs<DT, WIND>(P, xs, u, kv, WIND ? wind + 3 * b : nullptr);
 #pragma unroll
-        for (int i = 0; i < NK; ++i) x[i] = acc[i];
+        for (int i = 0; i < NK; ++i) x[i] = rk_axpy<DT, ST>(w6, kv[i], acc[i]);
     }
     double* ab = AB + ((size_t)b * N + k) * (NK * 16);
 #pragma unroll

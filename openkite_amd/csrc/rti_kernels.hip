@@ -371,24 +371,30 @@ __global__ __launch_bounds__(RK1_T, 1) void k_rk4_sens1(ModelConst P, int B, int
     for (int i = 0; i < NK; ++i) x[i] = Dual(xk[i], d == i ? 1.0 : 0.0);
 #pragma unroll
     for (int j = 0; j < NKU; ++j) u[j] = Dual(uk[j], d == NK + j ? 1.0 : 0.0);
+    // stages peeled at both ends as in rk4_sens2_body.inc (same bits)
+    const double w6 = h / 6.0, w3 = h / 3.0, hh = 0.5 * h;
 #pragma unroll 1
     for (int m = 0; m < M; ++m) {
         Dual xs[NK], acc[NK], kv[NK];
+        kite_rhs<Dual, false>(P, x, u, kv, nullptr);
 #pragma unroll
-        for (int i = 0; i < NK; ++i) { xs[i] = x[i]; acc[i] = x[i]; }
+        for (int i = 0; i < NK; ++i) {
+            acc[i] = Dual(fma(w6, kv[i].v, x[i].v), fma(w6, kv[i].t, x[i].t));
+            xs[i] = Dual(fma(hh, kv[i].v, x[i].v), fma(hh, kv[i].t, x[i].t));
+        }
 #pragma unroll 1
-        for (int st = 0; st < 4; ++st) {
+        for (int st = 1; st < 3; ++st) {
             kite_rhs<Dual, false>(P, xs, u, kv, nullptr);
-            const double wa = (st == 0 || st == 3) ? h / 6.0 : h / 3.0;
-            const double wn = (st < 2) ? 0.5 * h : h;
+            const double wn = (st < 2) ? hh : h;
 #pragma unroll
             for (int i = 0; i < NK; ++i) {
-                acc[i] = Dual(fma(wa, kv[i].v, acc[i].v), fma(wa, kv[i].t, acc[i].t));
+                acc[i] = Dual(fma(w3, kv[i].v, acc[i].v), fma(w3, kv[i].t, acc[i].t));
                 xs[i] = Dual(fma(wn, kv[i].v, x[i].v), fma(wn, kv[i].t, x[i].t));
             }
         }
+        kite_rhs<Dual, false>(P, xs, u, kv, nullptr);
 #pragma unroll
-        for (int i = 0; i < NK; ++i) x[i] = acc[i];
+        for (int i = 0; i < NK; ++i) x[i] = Dual(fma(w6, kv[i].v, acc[i].v), fma(w6, kv[i].t, acc[i].t));
     }
     double* ab = AB + ((size_t)b * N + k) * (NK * 16);
 #pragma unroll
