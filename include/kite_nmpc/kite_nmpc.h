@@ -776,6 +776,82 @@ int kite_nmpc_get_qp(kite_nmpc_ctx* ctx, int32_t instance, double* H, double* h,
 int kite_nmpc_batch(const kite_nmpc_ctx* ctx);
 int kite_nmpc_api_version(void);
 
+/* ---- closed-loop scoring (score_kernels.hip; no reference counterpart) ----
+ * What a flown episode is judged by, kept on the device: one launch per
+ * control period reads the true kite state and the control applied and adds
+ * the period to a row of fp64 accumulators per kite; a second kernel reduces
+ * the rows to a fleet summary.  The path, Q, R, Sx and Su are the context's
+ * configuration; `count` need not be the context's batch.  Additive to API 7.
+ *
+ * The distance is the true cross-track error: the distance to the GLOBAL
+ * closest point of the path (64 samples of theta, then a safeguarded Newton
+ * iteration clamped to the best sample's neighbours), not the distance to the
+ * plan's virtual theta0 (kite_mpc_diagnostic.pos_error) and not the local
+ * warm-start search of kite_nmpc_closest_point.                              */
+#define KITE_SCORE_NACC 16   /* doubles per kite in acc  */
+#define KITE_SCORE_NSUM 16   /* doubles of the summary   */
+#define KITE_SCORE_NMEM 8    /* doubles per kite in mem  */
+/* acc row of one kite; all zero = reset.  Slots 0-2 and 11-14 hold integers. */
+#define KITE_SCORE_N              0   /* scored periods                                          */
+#define KITE_SCORE_N_LOST         1   /* lost periods                                            */
+#define KITE_SCORE_EVER_LOST      2   /* 1 once a period was lost                                */
+#define KITE_SCORE_SUM_D2         3   /* sum d^2 [m^2], d = ||P(theta*) - r||                     */
+#define KITE_SCORE_MAX_D          4   /* max d [m] (meaningful when N > 0)                       */
+#define KITE_SCORE_SUM_TRACK      5   /* sum_a Q_a (Sx[6+a] (P(theta*) - r)_a)^2, summed          */
+#define KITE_SCORE_SUM_U          6   /* sum_i R_i (Su_i u_i)^2, summed                          */
+#define KITE_SCORE_SUM_RATE       7   /* ||Su (u - u_prev)||^2, summed over N_RATE periods       */
+#define KITE_SCORE_SUM_SPEED      8   /* sum ||v_b|| [m/s]                                       */
+#define KITE_SCORE_MIN_SPEED      9   /* min ||v_b|| [m/s] (meaningful when N > 0)               */
+#define KITE_SCORE_PROGRESS      10   /* sum wrap(theta* - theta*_prev) [rad], wrap to (-pi, pi];
+                                         laps = progress / 2 pi                                  */
+#define KITE_SCORE_N_MIN_SPEED   11   /* scored periods with KITE_ST_MIN_SPEED                   */
+#define KITE_SCORE_N_QP_NOT_CONV 12   /* scored periods with KITE_ST_QP_NOT_CONV                 */
+#define KITE_SCORE_N_STATE_BOUND 13   /* scored periods with KITE_ST_STATE_BOUND                 */
+#define KITE_SCORE_N_RATE        14   /* periods that added to SUM_RATE and PROGRESS             */
+#define KITE_SCORE_SPARE         15   /* 0                                                       */
+/* The summary holds the same slots over the kites as RAW values: sums, except
+ * the max of MAX_D and the min of MIN_SPEED (over the kites with N > 0; 0 when
+ * there is none), and in slot 15 the number of rows reduced.  Summaries of
+ * shards therefore combine by +, max and min (a shard with N = 0 has no max
+ * and no min).                                                               */
+#define KITE_SCORE_KITES         15
+/* mem row of one kite; all zero = reset */
+#define KITE_SCORE_MEM_THETA      0   /* theta* of the last scored period                        */
+#define KITE_SCORE_MEM_U          1   /* u4 of the last scored period (slots 1-4)                */
+#define KITE_SCORE_MEM_VALID      5   /* 1: slots 0-4 are the period before this one             */
+                                      /* slots 6, 7: spare                                       */
+
+/* theta* in [-2 pi / 64, 2 pi) and d = ||P(theta*) - pos|| of the global closest
+ * point for `count` positions (count x 3).  A non-finite position gives NaN
+ * in both.  Host pointers; _device: device pointers, asynchronous on the
+ * context's stream.                                                          */
+int kite_nmpc_closest_point_global(kite_nmpc_ctx* ctx, int32_t count, const double* pos3,
+                                   double* theta_out, double* dist_out);
+int kite_nmpc_closest_point_global_device(kite_nmpc_ctx* ctx, int32_t count, const double* d_pos3,
+                                          double* d_theta_out, double* d_dist_out);
+/* Score one control period of `count` kites: x13 (count x 13) the true state at
+ * t0, u4 (count x 4) the control applied from t0, status the controller's
+ * status words and plant_status the plant's (count each, either may be NULL),
+ * first != 0 at the start of an episode (no rate and no progress against the
+ * period before).  acc (count x 16) and mem (count x 8) are updated in place.
+ * A period is LOST when the plant status has KITE_PLANT_NAN, x13 or u4 is
+ * non-finite (or so large that a scored quantity overflows), or the
+ * controller status has KITE_ST_NAN, KITE_ST_STEP_REJECTED or
+ * KITE_ST_RESTART: it adds 1 to N_LOST, sets EVER_LOST, clears MEM_VALID (the
+ * next period adds no rate and no progress) and touches nothing else.  Any
+ * other period is scored into the slots above, with plain fp64 additions in
+ * call order; a kite's row depends on its own inputs only.                  */
+int kite_nmpc_score_step(kite_nmpc_ctx* ctx, int32_t count, const double* x13, const double* u4,
+                         const int32_t* status, const int32_t* plant_status, int32_t first,
+                         double* acc, double* mem);
+int kite_nmpc_score_step_device(kite_nmpc_ctx* ctx, int32_t count, const double* d_x13, const double* d_u4,
+                                const int32_t* d_status, const int32_t* d_plant_status, int32_t first,
+                                double* d_acc, double* d_mem);
+/* out16 (KITE_SCORE_NSUM) from acc (count x 16), in a fixed order without
+ * atomics: two calls on the same acc agree bit for bit.                     */
+int kite_nmpc_score_summary(kite_nmpc_ctx* ctx, int32_t count, const double* acc, double* out16);
+int kite_nmpc_score_summary_device(kite_nmpc_ctx* ctx, int32_t count, const double* d_acc, double* d_out16);
+
 #ifdef __cplusplus
 }
 #endif

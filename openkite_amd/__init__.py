@@ -11,6 +11,10 @@ from .nmpc import (BatchNMPC, CollocConfig, KiteEKF, KiteNMPF, KiteNmpcError, Ki
                    IdentConfig, IdentResult, ident_default_config, ident_param_index, ident_workspace_doubles,
                    save_properties, IDENT_FIELDS, IDENT_NP, IDENT_CHUNK, IDENT_NAN, IDENT_CONVERGED, IDENT_AT_BOUND,
                    IdentWindConfig, ident_wind_default_config, ident_joint_workspace_doubles, IDENT_WIND_AT_BOUND,
-                   IDENT_NPW)
+                   IDENT_NPW, score_combine, score_derive, SCORE_SLOTS, SCORE_NACC, SCORE_NSUM, SCORE_NMEM,
+                   SCORE_N, SCORE_N_LOST, SCORE_EVER_LOST, SCORE_SUM_D2, SCORE_MAX_D, SCORE_SUM_TRACK, SCORE_SUM_U,
+                   SCORE_SUM_RATE, SCORE_SUM_SPEED, SCORE_MIN_SPEED, SCORE_PROGRESS, SCORE_N_MIN_SPEED,
+                   SCORE_N_QP_NOT_CONV, SCORE_N_STATE_BOUND, SCORE_N_RATE, SCORE_SPARE, SCORE_KITES,
+                   SCORE_MEM_THETA, SCORE_MEM_U, SCORE_MEM_VALID)
 
 __version__ = "0.1.0"

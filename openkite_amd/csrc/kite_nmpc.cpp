@@ -23,6 +23,7 @@
 #include "kin_model.hpp"
 #include "kite_model_dp.hpp"
 #include "rti_kernels.hpp"
+#include "score_kernels.hpp"
 
 using kite::ModelConst;
 using kite::RtiConst;
@@ -1913,6 +1914,120 @@ int kite_nmpc_closest_point(kite_nmpc_ctx* ctx, int32_t count, const double* pos
     return run_items(ctx, {{pos, c * 3}, {guess ? guess : g.data(), c}}, {{theta_out, c}},
                      [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
                          return kite::launch_closest_point(ctx->rc, count, i[0], i[1], o[0], s);
+                     });
+}
+
+// ---- closed-loop scoring (score_kernels.hip) ---------------------------------
+static_assert(KITE_SCORE_NACC == kite::kScoreNacc && KITE_SCORE_NSUM == kite::kScoreNsum &&
+                  KITE_SCORE_NMEM == kite::kScoreNmem && KITE_SCORE_N == kite::kScoreN &&
+                  KITE_SCORE_N_LOST == kite::kScoreNLost && KITE_SCORE_EVER_LOST == kite::kScoreEverLost &&
+                  KITE_SCORE_SUM_D2 == kite::kScoreSumD2 && KITE_SCORE_MAX_D == kite::kScoreMaxD &&
+                  KITE_SCORE_SUM_TRACK == kite::kScoreSumTrack && KITE_SCORE_SUM_U == kite::kScoreSumU &&
+                  KITE_SCORE_SUM_RATE == kite::kScoreSumRate && KITE_SCORE_SUM_SPEED == kite::kScoreSumSpeed &&
+                  KITE_SCORE_MIN_SPEED == kite::kScoreMinSpeed && KITE_SCORE_PROGRESS == kite::kScoreProgress &&
+                  KITE_SCORE_N_MIN_SPEED == kite::kScoreNMinSpeed &&
+                  KITE_SCORE_N_QP_NOT_CONV == kite::kScoreNQpNotConv &&
+                  KITE_SCORE_N_STATE_BOUND == kite::kScoreNStateBound && KITE_SCORE_N_RATE == kite::kScoreNRate &&
+                  KITE_SCORE_SPARE == kite::kScoreSpare && KITE_SCORE_KITES == kite::kScoreKites &&
+                  KITE_SCORE_MEM_THETA == kite::kScoreMemTheta && KITE_SCORE_MEM_U == kite::kScoreMemU &&
+                  KITE_SCORE_MEM_VALID == kite::kScoreMemValid,
+              "the kernels' slot layout is the header's");
+static_assert(KITE_ST_NAN == kite::kStNan && KITE_ST_QP_NOT_CONV == kite::kStQpNotConv &&
+                  KITE_ST_MIN_SPEED == kite::kStMinSpeed && KITE_ST_STATE_BOUND == kite::kStStateBound &&
+                  KITE_ST_STEP_REJECTED == kite::kStStepRejected && KITE_ST_RESTART == kite::kStRestart &&
+                  KITE_PLANT_NAN == kite::kPlantNan,
+              "the scorer reads the header's status bits");
+
+extern "C++" {
+namespace {
+// the scorer's constants from the configuration in force
+kite::ScoreConst make_score_const(const kite_nmpc_ctx* ctx) {
+    const kite_nmpc_config& c = ctx->cfg;
+    const RtiConst& rc = ctx->rc;
+    kite::ScoreConst S;
+    std::memset(&S, 0, sizeof(S));
+    S.path_K = rc.path_K;
+    S.path_R = rc.path_R;
+    S.path_alt = rc.path_alt;
+    for (int i = 0; i < 4; ++i) S.pq[i] = rc.pq[i];
+    for (int a = 0; a < 3; ++a) { S.Q[a] = c.Q[a]; S.Sr[a] = c.Sx[6 + a]; }
+    for (int i = 0; i < 4; ++i) { S.R[i] = c.R[i]; S.Su[i] = c.Su[i]; }
+    std::memcpy(S.pF, rc.pF, sizeof(S.pF));
+    return S;
+}
+}  // namespace
+}  // extern "C++"
+
+int kite_nmpc_closest_point_global_device(kite_nmpc_ctx* ctx, int32_t count, const double* d_pos3,
+                                          double* d_theta_out, double* d_dist_out) {
+    if (!ctx || count < 1 || !d_pos3 || !d_theta_out || !d_dist_out) return KITE_EINVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(kite::launch_closest_point_global(make_score_const(ctx), count, d_pos3, d_theta_out, d_dist_out,
+                                              ctx->stream));
+    return KITE_OK;
+}
+
+int kite_nmpc_closest_point_global(kite_nmpc_ctx* ctx, int32_t count, const double* pos3, double* theta_out,
+                                   double* dist_out) {
+    if (!ctx || count < 1 || !pos3 || !theta_out || !dist_out) return KITE_EINVAL;
+    const size_t c = count;
+    const kite::ScoreConst S = make_score_const(ctx);
+    return run_items(ctx, {{pos3, c * 3}}, {{theta_out, c}, {dist_out, c}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         return kite::launch_closest_point_global(S, count, i[0], o[0], o[1], s);
+                     });
+}
+
+int kite_nmpc_score_step_device(kite_nmpc_ctx* ctx, int32_t count, const double* d_x13, const double* d_u4,
+                                const int32_t* d_status, const int32_t* d_plant_status, int32_t first, double* d_acc,
+                                double* d_mem) {
+    if (!ctx || count < 1 || !d_x13 || !d_u4 || !d_acc || !d_mem) return KITE_EINVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(kite::launch_score(make_score_const(ctx), count, d_x13, d_u4, d_status, d_plant_status, first != 0,
+                               d_acc, d_mem, ctx->stream));
+    return KITE_OK;
+}
+
+int kite_nmpc_score_step(kite_nmpc_ctx* ctx, int32_t count, const double* x13, const double* u4,
+                         const int32_t* status, const int32_t* plant_status, int32_t first, double* acc,
+                         double* mem) {
+    if (!ctx || count < 1 || !x13 || !u4 || !acc || !mem) return KITE_EINVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t c = count;
+    const size_t nx = c * 13, nu = c * 4, na = c * KITE_SCORE_NACC, nm = c * KITE_SCORE_NMEM, ns = (c + 1) / 2;
+    int rc = ensure_scratch(ctx, (nx + nu + na + nm + 2 * ns) * sizeof(double));
+    if (rc) return rc;
+    double *dx = ctx->scratch, *du = dx + nx, *da = du + nu, *dm = da + na;
+    int32_t* dst = reinterpret_cast<int32_t*>(dm + nm);
+    int32_t* dps = reinterpret_cast<int32_t*>(dm + nm + ns);
+    hipStream_t s = ctx->stream;
+    HIP_TRY(hipMemcpyAsync(dx, x13, nx * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(du, u4, nu * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(da, acc, na * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dm, mem, nm * sizeof(double), hipMemcpyHostToDevice, s));
+    if (status) HIP_TRY(hipMemcpyAsync(dst, status, c * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (plant_status) HIP_TRY(hipMemcpyAsync(dps, plant_status, c * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(kite::launch_score(make_score_const(ctx), count, dx, du, status ? dst : nullptr,
+                               plant_status ? dps : nullptr, first != 0, da, dm, s));
+    HIP_TRY(hipMemcpyAsync(acc, da, na * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(mem, dm, nm * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return KITE_OK;
+}
+
+int kite_nmpc_score_summary_device(kite_nmpc_ctx* ctx, int32_t count, const double* d_acc, double* d_out16) {
+    if (!ctx || count < 1 || !d_acc || !d_out16) return KITE_EINVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(kite::launch_score_summary(count, d_acc, d_out16, ctx->stream));
+    return KITE_OK;
+}
+
+int kite_nmpc_score_summary(kite_nmpc_ctx* ctx, int32_t count, const double* acc, double* out16) {
+    if (!ctx || count < 1 || !acc || !out16) return KITE_EINVAL;
+    const size_t c = count;
+    return run_items(ctx, {{acc, c * KITE_SCORE_NACC}}, {{out16, KITE_SCORE_NSUM}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         return kite::launch_score_summary(count, i[0], o[0], s);
                      });
 }
 

@@ -45,6 +45,16 @@ One step of a fleet of kites on one rank:
          identification fits the model that sees it
          (kite_nmpc_identify_wind_device).
 
+  score  with ``scorer`` (an ``EpisodeScore``): right after the RTI the period
+         is scored on the stream (kite_nmpc_score_step_device, one launch): the
+         true state at t0 (the plant's; without one the state the plan started
+         from), the control just computed and the two status words go into
+         per-kite accumulators -- the true cross-track error against the
+         global closest point of the path, the controller's costs there, the
+         control rate, the airspeed, the progress round the path, the lost
+         periods.  ``restart`` marks the next period as an episode's first;
+         the accumulators persist until ``scorer.reset()``.
+
 The stepper does the arithmetic; ``GpuStepper`` drives libkite_nmpc.so on
 device tensors.  Tests plug a CPU oracle stepper into the same loop to check
 the sharded multi-rank flow against the unsharded batch.
@@ -125,6 +135,75 @@ class GpuStepper:
                                        X.data_ptr(), U.data_ptr(), out.data_ptr(), wind_out.data_ptr(),
                                        cost2.data_ptr(), evals.data_ptr(), status.data_ptr(), ws.data_ptr(),
                                        wind0=W0.data_ptr() if W0 is not None else 0)
+
+    def score(self, x13, u4, status, plant_status, first, acc, mem):
+        """One control period of every kite into the accumulators acc (B, 16) and
+        mem (B, 8), one launch on the stream (kite_nmpc_score_step_device); x13
+        (B, 13) and u4 (B, 4) contiguous, status / plant_status (B,) int32 or None."""
+        assert x13.dtype == torch.float64 and x13.is_contiguous() and u4.is_contiguous()
+        self.ctx.score_step_device(x13.shape[0], x13.data_ptr(), u4.data_ptr(),
+                                   status.data_ptr() if status is not None else 0,
+                                   plant_status.data_ptr() if plant_status is not None else 0, first,
+                                   acc.data_ptr(), mem.data_ptr())
+
+    def score_summary(self, acc, out):
+        """out (16,) <- the raw fleet summary of acc (B, 16), on the stream."""
+        self.ctx.score_summary_device(acc.shape[0], acc.data_ptr(), out.data_ptr())
+
+
+class EpisodeScore:
+    """Per-kite flight metrics of a fleet on the device, filled one launch per
+    control period by ``FleetLoop(scorer=...)`` (or by ``GpuStepper.score``):
+    acc (B, 16) the accumulator rows (slots ``nmpc.SCORE_*``), mem (B, 8) what
+    a period needs of the one before, ``first`` the flag of the period that
+    starts an episode.  The accumulators persist across episodes: ``reset``
+    alone clears them.  Nothing here synchronises except ``summary``, which
+    brings 16 doubles to the host."""
+
+    def __init__(self, B: int, device=None):
+        self.B = int(B)
+        f64 = dict(dtype=torch.float64, device=device)
+        self.acc = torch.zeros((self.B, 16), **f64)
+        self.mem = torch.zeros((self.B, 8), **f64)
+        self._sum = torch.zeros((16,), **f64)
+        self.first = True
+        self.stepper, self.dt = None, None         # set by the loop that scores into this
+
+    def reset(self):
+        self.acc.zero_()
+        self.mem.zero_()
+        self.first = True
+
+    def rows(self) -> dict:
+        """The accumulator rows by name, (B,) tensors each (views of acc)."""
+        from . import nmpc
+        return {name: self.acc[:, i] for i, name in enumerate(nmpc.SCORE_SLOTS)}
+
+    def summary(self, stepper=None, dt: Optional[float] = None) -> dict:
+        """The fleet summary: the raw 16 ("raw", a list: what ``combine`` takes)
+        and the figures derived from them (``nmpc.score_derive``).  The
+        reduction runs on ``stepper`` (default: the stepper and the dt of the
+        loop this scorer was given to)."""
+        from . import nmpc
+        stepper = stepper if stepper is not None else self.stepper
+        if stepper is None:
+            raise ValueError("EpisodeScore.summary: no stepper (give one, or give the scorer to a FleetLoop)")
+        dt = dt if dt is not None else self.dt
+        stepper.score_summary(self.acc, self._sum)
+        raw = self._sum.cpu().numpy().copy()
+        out = nmpc.score_derive(raw, dt)
+        out["raw"] = raw.tolist()
+        return out
+
+    @staticmethod
+    def combine(raw_summaries, dt: Optional[float] = None) -> dict:
+        """The summary of several ranks' raw summaries (gathered by any means):
+        host arithmetic, no GPU."""
+        from . import nmpc
+        raw = nmpc.score_combine(raw_summaries)
+        out = nmpc.score_derive(raw, dt)
+        out["raw"] = raw.tolist()
+        return out
 
 
 class GpuPlant:
@@ -247,7 +326,9 @@ class FleetLoop:
                  covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None,
                  plant=None, wind_ekf: bool = False, wind_max: float = 20.0, recorder=None, adapt=None,
                  estimator_model: str = "creation", ident_wind=None, kin_ekf: bool = False,
-                 ident_wind_config=None):
+                 ident_wind_config=None, scorer=None):
+        if scorer is not None and scorer.B != x0.shape[0]:
+            raise ValueError(f"the scorer holds {scorer.B} kites, the loop flies {x0.shape[0]}")
         if ekf and wind_ekf:
             raise ValueError("ekf and wind_ekf are two estimators: choose one")
         if kin_ekf and (ekf or wind_ekf):
@@ -391,6 +472,14 @@ class FleetLoop:
             self.xp = x0[:, :13].clone().contiguous()
             self.t = 0.0
             self.plant_status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        # a scorer (``EpisodeScore``): every period is scored right after the RTI,
+        # one launch on the stream, from the true state at t0 and the control
+        # just computed; None: no call is made
+        self.scorer = scorer
+        if scorer is not None:
+            scorer.stepper, scorer.dt = stepper, dt
+            if plant is None:
+                self._score_x = torch.zeros((B, 13), **f64)
 
     def restart(self):
         """Start the next episode: every kite back at its launch state, the
@@ -399,6 +488,8 @@ class FleetLoop:
         self.stepper.reset()
         self.x0.copy_(self.x_init)
         self.u0.zero_()
+        if self.scorer is not None:
+            self.scorer.first = True   # the accumulators go on; the next period has no predecessor
         if self.adapt is not None:
             self.recorder.reset()      # a log does not span episodes; the adapted models (and wind) stay
         if self.plant is not None:
@@ -497,6 +588,16 @@ class FleetLoop:
             if self.adapt is not None and self.recorder.full:
                 self._adapt()
         self.stepper.rti(self.x0, self.u0, self.traj, self.diag, self.status)
+        if self.scorer is not None:
+            # the true state at t0: the plant's, or without one the state the plan
+            # started from (the loop's plant is then the plan itself)
+            sc = self.scorer
+            if self.plant is not None:
+                self.stepper.score(self.xp, self.u0, self.status, self.plant_status, sc.first, sc.acc, sc.mem)
+            else:
+                self._score_x.copy_(self.x0[:, :13])
+                self.stepper.score(self._score_x, self.u0, self.status, None, sc.first, sc.acc, sc.mem)
+            sc.first = False
         if self.recorder is not None:
             if self.ident_joint:
                 # the known part W0 of the joint model's wind: the wind EKF's estimate

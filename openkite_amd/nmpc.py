@@ -35,6 +35,16 @@ EST_MODEL_CREATION = 0             # KITE_EST_MODEL_*: the model of the two EKFs
 EST_MODEL_CONTROLLER = 1
 IDENT_NP = 21                      # KITE_IDENT_NP
 IDENT_CHUNK = 8                    # KITE_IDENT_CHUNK: samples per partial sum of k_ident_accum
+# closed-loop scoring (KITE_SCORE_*): doubles per kite in acc / mem, doubles of the summary, and the slots
+SCORE_NACC, SCORE_NSUM, SCORE_NMEM = 16, 16, 8
+(SCORE_N, SCORE_N_LOST, SCORE_EVER_LOST, SCORE_SUM_D2, SCORE_MAX_D, SCORE_SUM_TRACK, SCORE_SUM_U, SCORE_SUM_RATE,
+ SCORE_SUM_SPEED, SCORE_MIN_SPEED, SCORE_PROGRESS, SCORE_N_MIN_SPEED, SCORE_N_QP_NOT_CONV, SCORE_N_STATE_BOUND,
+ SCORE_N_RATE, SCORE_SPARE) = range(16)
+SCORE_KITES = 15                   # summary only: the number of rows reduced
+SCORE_MEM_THETA, SCORE_MEM_U, SCORE_MEM_VALID = 0, 1, 5
+# names of the acc slots (the summary's slot 15 is "kites")
+SCORE_SLOTS = ["n", "n_lost", "ever_lost", "sum_d2", "max_d", "sum_track", "sum_u", "sum_rate", "sum_speed",
+               "min_speed", "progress", "n_min_speed", "n_qp_not_conv", "n_state_bound", "n_rate", "spare"]
 # the identified parameters in the reference's REF_P order (kite_identification_test.cpp:120-121)
 IDENT_FIELDS = ["CL0", "CLa_total", "CD0_total", "CYb", "Cm0", "Cma", "Cnb", "Clb", "CLq", "Cmq",
                 "CYr", "Cnr", "Clr", "CYp", "Clp", "Cnp", "CLde", "CYdr", "Cmde", "Cndr", "Cldr"]
@@ -312,6 +322,17 @@ _SIGNATURES = {
     "kite_nmpc_plant_step_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_void_p]),
+    "kite_nmpc_closest_point_global": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP]),
+    "kite_nmpc_closest_point_global_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                             ctypes.c_void_p, ctypes.c_void_p]),
+    "kite_nmpc_score_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _IP, _IP, ctypes.c_int32,
+                                            _DP, _DP]),
+    "kite_nmpc_score_step_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                   ctypes.c_void_p]),
+    "kite_nmpc_score_summary": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _DP, _DP]),
+    "kite_nmpc_score_summary_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                      ctypes.c_void_p]),
 }
 
 
@@ -659,6 +680,53 @@ class BatchNMPC:
         g = None if guess is None else _f64(guess).reshape(-1)
         _check(lib().kite_nmpc_closest_point(self._h, pos.shape[0], _p(pos), _p(g), _p(out)), "closest_point")
         return out
+
+    # --- closed-loop scoring ----------------------------------------------------
+    def closest_point_global(self, pos):
+        """The global closest point of the path to every position (count, 3):
+        (theta* in [-2 pi / 64, 2 pi), d = ||P(theta*) - pos||), NaN for a
+        non-finite position (kite_nmpc_closest_point_global)."""
+        pos = _f64(pos).reshape(-1, 3)
+        th = np.zeros(pos.shape[0]); d = np.zeros(pos.shape[0])
+        _check(lib().kite_nmpc_closest_point_global(self._h, pos.shape[0], _p(pos), _p(th), _p(d)),
+               "closest_point_global")
+        return th, d
+
+    def closest_point_global_device(self, count: int, d_pos3: int, d_theta: int, d_dist: int):
+        _check(lib().kite_nmpc_closest_point_global_device(self._h, int(count), d_pos3, d_theta, d_dist),
+               "closest_point_global_device")
+
+    def score_step(self, x13, u4, acc, mem, status=None, plant_status=None, first: bool = False):
+        """One control period of every kite into acc (count, 16) and mem
+        (count, 8), both updated in place and returned (kite_nmpc_score_step;
+        the slots are SCORE_*).  status / plant_status: (count,) int32 words."""
+        x = _f64(x13).reshape(-1, 13); u = _f64(u4).reshape(-1, 4)
+        c = x.shape[0]
+        assert u.shape[0] == c and acc.shape == (c, SCORE_NACC) and mem.shape == (c, SCORE_NMEM)
+        st = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(c)
+        ps = None if plant_status is None else np.ascontiguousarray(plant_status, dtype=np.int32).reshape(c)
+        _check(lib().kite_nmpc_score_step(self._h, c, _p(x), _p(u), st.ctypes.data_as(_IP) if st is not None else None,
+                                          ps.ctypes.data_as(_IP) if ps is not None else None, int(bool(first)),
+                                          _p(acc), _p(mem)), "score_step")
+        return acc, mem
+
+    def score_step_device(self, count: int, d_x13: int, d_u4: int, d_status: int, d_plant_status: int, first: bool,
+                          d_acc: int, d_mem: int):
+        """Device pointers, asynchronous on the context's stream (0: no status word)."""
+        _check(lib().kite_nmpc_score_step_device(self._h, int(count), d_x13, d_u4, d_status or None,
+                                                 d_plant_status or None, int(bool(first)), d_acc, d_mem),
+               "score_step_device")
+
+    def score_summary(self, acc):
+        """The raw fleet summary (16,) of acc (count, 16) (kite_nmpc_score_summary);
+        ``score_derive`` makes the readable figures from it."""
+        a = _f64(acc).reshape(-1, SCORE_NACC)
+        out = np.zeros(SCORE_NSUM)
+        _check(lib().kite_nmpc_score_summary(self._h, a.shape[0], _p(a), _p(out)), "score_summary")
+        return out
+
+    def score_summary_device(self, count: int, d_acc: int, d_out16: int):
+        _check(lib().kite_nmpc_score_summary_device(self._h, int(count), d_acc, d_out16), "score_summary_device")
 
     def dynamics(self, x15, u4):
         x = _f64(x15).reshape(-1, 15); u = _f64(u4).reshape(-1, 4)
@@ -1152,6 +1220,51 @@ def path_eval(config: NmpcConfig, theta):
     P = np.zeros((th.size, 3)); dP = np.zeros((th.size, 3))
     _check(lib().kite_nmpc_path_eval(ctypes.byref(config), th.size, _p(th), _p(P), _p(dP)), "path_eval")
     return P, dP
+
+
+def score_combine(summaries) -> np.ndarray:
+    """One raw summary (16,) from the raw summaries of several shards or ranks:
+    slot by slot +, except max over SCORE_MAX_D and min over SCORE_MIN_SPEED,
+    both over the summaries that scored a period (n > 0).  Host arithmetic."""
+    S = [np.asarray(s, dtype=np.float64).reshape(SCORE_NSUM) for s in summaries]
+    if not S:
+        raise ValueError("score_combine: no summary")
+    out = np.zeros(SCORE_NSUM)
+    for s in S:                                     # in list order: reproducible
+        out += s
+    scored = [s for s in S if s[SCORE_N] > 0]
+    out[SCORE_MAX_D] = max((s[SCORE_MAX_D] for s in scored), default=0.0)
+    out[SCORE_MIN_SPEED] = min((s[SCORE_MIN_SPEED] for s in scored), default=0.0)
+    return out
+
+
+def score_derive(raw, dt: Optional[float] = None) -> dict:
+    """The readable figures of a raw summary (16,): the raw slots by name
+    (SCORE_SLOTS, slot 15 as "kites") and rms_d [m], mean_track, mean_u,
+    mean_speed per scored period, mean_rate per period that has a predecessor,
+    lost_fraction of all periods, kites_lost_fraction, laps (progress / 2 pi
+    summed over the kites) and laps_per_kite; with dt [s] also lap_rate, the
+    mean laps per second of flight between scored periods.  A ratio without
+    a denominator is NaN."""
+    raw = np.asarray(raw, dtype=np.float64).reshape(SCORE_NSUM)
+    out = {name: float(raw[i]) for i, name in enumerate(SCORE_SLOTS[:15])}
+    out["kites"] = float(raw[SCORE_KITES])
+
+    def ratio(a, b):
+        return float(a / b) if b > 0 else float("nan")
+    n, nl, nr = raw[SCORE_N], raw[SCORE_N_LOST], raw[SCORE_N_RATE]
+    out["rms_d"] = float(np.sqrt(ratio(raw[SCORE_SUM_D2], n)))
+    out["mean_track"] = ratio(raw[SCORE_SUM_TRACK], n)
+    out["mean_u"] = ratio(raw[SCORE_SUM_U], n)
+    out["mean_speed"] = ratio(raw[SCORE_SUM_SPEED], n)
+    out["mean_rate"] = ratio(raw[SCORE_SUM_RATE], nr)
+    out["lost_fraction"] = ratio(nl, n + nl)
+    out["kites_lost_fraction"] = ratio(raw[SCORE_EVER_LOST], raw[SCORE_KITES])
+    out["laps"] = float(raw[SCORE_PROGRESS] / (2.0 * np.pi))
+    out["laps_per_kite"] = ratio(raw[SCORE_PROGRESS] / (2.0 * np.pi), raw[SCORE_KITES])
+    if dt is not None:
+        out["lap_rate"] = ratio(raw[SCORE_PROGRESS] / (2.0 * np.pi), nr * dt)
+    return out
 
 
 def colloc_default_config(**overrides) -> CollocConfig:
