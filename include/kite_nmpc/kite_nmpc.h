@@ -546,6 +546,29 @@ int kite_nmpc_get_params(kite_nmpc_ctx* ctx, kite_params* out);
 int kite_nmpc_set_estimator_model(kite_nmpc_ctx* ctx, int32_t mode);
 int kite_nmpc_get_estimator_model(kite_nmpc_ctx* ctx, int32_t* mode);
 
+/* ---- two-phase tiled QP (additive, no version change) ----------------------
+ * At N = 20 with the tiled QP (qp_kernel 2) the main solve can run in two
+ * launches: the first stops every kite that has not converged at the top of
+ * interior-point iteration `split_iteration` (a constant of the build), the
+ * second resumes them from a checkpoint, dispatched by their residual at that
+ * point, largest first -- the waves of a large batch queue per SIMD, and this
+ * order shortens the tail of the launch.  Every kite's result is bit for bit
+ * the one-launch solve's.
+ *   KITE_QP_SPLIT_AUTO   (default) split when the batch is large enough for
+ *                        several waves to queue per SIMD on this device
+ *   KITE_QP_SPLIT_NEVER  one launch
+ *   mode > 0             split at any batch
+ * Any other horizon or qp_kernel: accepted and without effect.  mode < -1:
+ * KITE_EINVAL.  The getter's outputs are each nullable: the mode set, whether
+ * the next step splits (1 / 0), the build's split iteration, and how many
+ * launch sequences have been issued with the split since creation (a step
+ * replayed from a captured graph counts once, at its capture).               */
+#define KITE_QP_SPLIT_AUTO  (-1)
+#define KITE_QP_SPLIT_NEVER 0
+int kite_nmpc_set_qp_split(kite_nmpc_ctx* ctx, int32_t mode);
+int kite_nmpc_get_qp_split(kite_nmpc_ctx* ctx, int32_t* mode, int32_t* active, int32_t* split_iteration,
+                           int64_t* split_launches);
+
 /* ---- aerodynamic parameter identification (additive, no version change) ----
  * src/kite_control/kite_identification_test.cpp: fit the 21 aerodynamic
  * coefficients of a kite to a logged flight, batched over `count` kites.

@@ -7,7 +7,7 @@ from .nmpc import (BatchNMPC, CollocConfig, KiteEKF, KiteNMPF, KiteNmpcError, Ki
                    colloc_default_config, default_config, ekf_default_covariances, load_properties, lib, LIB_PATH, DIAG_FIELDS,
                    path_eval, perturb_params, resolve_qp_kernel, PERTURB_FIELDS, PLANT_NAN,
                    wind_ekf_default_covariances, EKF_NAN, EKF_S_NOT_PD, WIND_MAX_DEFAULT,
-                   EST_MODEL_CREATION, EST_MODEL_CONTROLLER, EKF_INIT_BAD, PoseFrame, pose_frame_default,
+                   EST_MODEL_CREATION, EST_MODEL_CONTROLLER, QP_SPLIT_AUTO, QP_SPLIT_NEVER, EKF_INIT_BAD, PoseFrame, pose_frame_default,
                    IdentConfig, IdentResult, ident_default_config, ident_param_index, ident_workspace_doubles,
                    save_properties, IDENT_FIELDS, IDENT_NP, IDENT_CHUNK, IDENT_NAN, IDENT_CONVERGED, IDENT_AT_BOUND,
                    IdentWindConfig, ident_wind_default_config, ident_joint_workspace_doubles, IDENT_WIND_AT_BOUND,

@@ -41,6 +41,9 @@ constexpr int KITE_NEV = 6;
 // synchronises on the last event before reading the elapsed times, and no
 // caller reads device memory through these events.
 constexpr unsigned kTimingEventFlags = hipEventDisableSystemFence;
+// kite_nmpc_set_qp_split's auto mode: the two-phase tiled QP from this many QP
+// waves per SIMD on (4 SIMDs per compute unit); 0: auto never splits
+constexpr int kQpSplitWavesPerSimd = 2;
 
 struct kite_nmpc_ctx {
     kite_params params;
@@ -90,6 +93,13 @@ struct kite_nmpc_ctx {
     double* wstep = nullptr;       // tiled path, 2 B n: physical QP step per kite (k_qp_tiled -> k_expand20), then
                                    // the scaled one (-> k_qp_tiled_lazy: round 0 handed over); N = 40:
                                    // round-0 solution of the kites k_qp_lds hands to k_qp_lds_lazy
+    // two-phase tiled QP (kite_nmpc_set_qp_split; qp_tiled.inc): the checkpoint
+    // of the kites the first phase hands on, their dispatch keys and order
+    double* qp_ckpt = nullptr;     // B x qp_split_ckpt_doubles(), allocated when a split can run
+    int32_t* qp_key = nullptr;     // 2 B: keys, then the second order
+    int qp_split_mode = KITE_QP_SPLIT_AUTO;
+    int qp_split_min_batch = 0;    // auto: split from this batch on (0: never)
+    long long qp_split_launches = 0;   // launch sequences issued (or captured) with the split
     // scratch for the model-level entry points
     double* scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -300,12 +310,13 @@ void free_ctx(kite_nmpc_ctx* ctx) {
     double** bufs[] = {&ctx->X, &ctx->U, &ctx->x0, &ctx->AB, &ctx->DEF, &ctx->Hs, &ctx->hs,
                        &ctx->Cr, &ctx->cl, &ctx->cu, &ctx->hmax, &ctx->u0, &ctx->diag, &ctx->kkt,
                        &ctx->scratch, &ctx->Htl, &ctx->Hab, &ctx->Hbb, &ctx->wstep, &ctx->wind,
-                       &ctx->plant_mc, &ctx->plant_wind, &ctx->model_tab, &ctx->model_rows};
+                       &ctx->plant_mc, &ctx->plant_wind, &ctx->model_tab, &ctx->model_rows, &ctx->qp_ckpt};
     for (double** p : bufs) if (*p) { (void)hipFree(*p); *p = nullptr; }
     if (ctx->dconst) { (void)hipFree(ctx->dconst); ctx->dconst = nullptr; }
     if (ctx->status) { (void)hipFree(ctx->status); ctx->status = nullptr; }
     if (ctx->iters) { (void)hipFree(ctx->iters); ctx->iters = nullptr; }
     if (ctx->order) { (void)hipFree(ctx->order); ctx->order = nullptr; }
+    if (ctx->qp_key) { (void)hipFree(ctx->qp_key); ctx->qp_key = nullptr; }
     for (auto& e : ctx->ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     for (auto& e : ctx->ring) if (e) (void)hipEventDestroy(e);
     ctx->ring.clear();
@@ -331,6 +342,25 @@ int upload_dconst(kite_nmpc_ctx* ctx, hipStream_t s) {
         ctx->dconst_stage.assign(blob, blob + sizeof(blob));
         HIP_TRY(hipMemcpyAsync(ctx->dconst, ctx->dconst_stage.data(), sizeof(blob), hipMemcpyHostToDevice, s));
         ctx->dconst_host.swap(ctx->dconst_stage);
+    }
+    return KITE_OK;
+}
+
+// whether the next step's main tiled QP runs in two launches
+bool qp_split_active(const kite_nmpc_ctx* ctx) {
+    if (!ctx->tiled || ctx->cfg.N != 20 || ctx->qp_split_mode == KITE_QP_SPLIT_NEVER) return false;
+    if (ctx->qp_split_mode > 0) return true;
+    return ctx->qp_split_min_batch > 0 && ctx->B >= ctx->qp_split_min_batch;
+}
+int ensure_qp_split_bufs(kite_nmpc_ctx* ctx) {
+    const size_t B = (size_t)ctx->B;
+    if (!ctx->qp_ckpt) {
+        HIP_TRY(hipMalloc(&ctx->qp_ckpt, B * kite::qp_split_ckpt_doubles() * sizeof(double)));
+        HIP_TRY(hipMemset(ctx->qp_ckpt, 0, B * kite::qp_split_ckpt_doubles() * sizeof(double)));
+    }
+    if (!ctx->qp_key) {
+        HIP_TRY(hipMalloc(&ctx->qp_key, 2 * B * sizeof(int32_t)));
+        HIP_TRY(hipMemset(ctx->qp_key, 0, 2 * B * sizeof(int32_t)));
     }
     return KITE_OK;
 }
@@ -377,11 +407,15 @@ int run_step(kite_nmpc_ctx* ctx, const double* x0) {
                                     ctx->diag, ctx->status, ctx->kkt, ctx->iters, ctx->iters + B, ctx->order,
                                     ctx->Hs, s, ev ? ev[5] : nullptr));
     }
-    else if (ctx->tiled)
+    else if (ctx->tiled) {
+        const kite::QpSplitBufs sb{ctx->qp_ckpt, ctx->qp_key, ctx->qp_key + B};
+        const bool split = qp_split_active(ctx);       // the buffers exist: created with the mode
+        if (split) ++ctx->qp_split_launches;
         HIP_TRY(kite::launch_qp_tiled(ctx->mc, ctx->rc, B, ctx->Htl, ctx->Hab, ctx->Hbb, ctx->hs, ctx->Cr, ctx->cl,
                                       ctx->cu, ctx->hmax, ctx->AB, ctx->DEF, ctx->X, ctx->U, ctx->u0, ctx->diag,
                                       ctx->status, ctx->kkt, ctx->iters, ctx->order, ctx->order + B, ctx->wstep,
-                                      s, ev ? ev[5] : nullptr));
+                                      s, ev ? ev[5] : nullptr, split ? &sb : nullptr));
+    }
     else
         HIP_TRY(kite::launch_qp(ctx->mc, ctx->rc, B, ctx->Hs, ctx->hs, ctx->Cr, ctx->cl, ctx->cu, ctx->hmax, ctx->AB,
                                 ctx->DEF, ctx->X, ctx->U, ctx->u0, ctx->diag, ctx->status, ctx->kkt, ctx->iters,
@@ -644,6 +678,19 @@ int kite_nmpc_create(const kite_params* params, const kite_nmpc_config* cfg, int
     // [B, 2B) QP iterations, [2B, 3B) steps ending outside the state box (status
     // bit 8), [3B, 4B) (node, state) pairs outside it (kite_nmpc_state_bound_stats)
     (void)hipMemset(ctx->iters, 0, 4 * B * sizeof(int32_t));
+    // two-phase QP, auto: where several QP waves queue per SIMD (one wave per
+    // SIMD at a time), B >= kQpSplitWavesPerSimd x the device's SIMD count
+    if (kQpSplitWavesPerSimd > 0) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0)
+            ctx->qp_split_min_batch = kQpSplitWavesPerSimd * 4 * cus;
+    }
+    {
+        // KITE_NMPC_QP_SPLIT=<mode>: the initial mode of kite_nmpc_set_qp_split (A/B runs)
+        const char* qs = std::getenv("KITE_NMPC_QP_SPLIT");
+        if (qs && qs[0]) ctx->qp_split_mode = std::max(KITE_QP_SPLIT_AUTO, std::atoi(qs));
+    }
+    if (qp_split_active(ctx) && ensure_qp_split_bufs(ctx) != KITE_OK) { free_ctx(ctx); delete ctx; return KITE_ENOMEM; }
     if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) {
         free_ctx(ctx); delete ctx; return KITE_EHIP;
     }
@@ -1168,6 +1215,30 @@ int estimator_model(const kite_nmpc_ctx* ctx, int32_t count, const ModelConst** 
 int kite_nmpc_set_estimator_model(kite_nmpc_ctx* ctx, int32_t mode) {
     if (!ctx || (mode != KITE_EST_MODEL_CREATION && mode != KITE_EST_MODEL_CONTROLLER)) return KITE_EINVAL;
     ctx->est_model = mode;       // read at each EKF call: no kernel of the captured step depends on it
+    return KITE_OK;
+}
+
+int kite_nmpc_set_qp_split(kite_nmpc_ctx* ctx, int32_t mode) {
+    if (!ctx || mode < KITE_QP_SPLIT_AUTO) return KITE_EINVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int old = ctx->qp_split_mode;
+    ctx->qp_split_mode = mode;
+    if (qp_split_active(ctx)) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        const int rc = ensure_qp_split_bufs(ctx);
+        if (rc) { ctx->qp_split_mode = old; return rc; }
+    }
+    ++ctx->graph_gen;                                // the mode selects other kernels
+    return KITE_OK;
+}
+
+int kite_nmpc_get_qp_split(kite_nmpc_ctx* ctx, int32_t* mode, int32_t* active, int32_t* split_iteration,
+                           int64_t* split_launches) {
+    if (!ctx) return KITE_EINVAL;
+    if (mode) *mode = ctx->qp_split_mode;
+    if (active) *active = qp_split_active(ctx) ? 1 : 0;
+    if (split_iteration) *split_iteration = kite::qp_split_iteration();
+    if (split_launches) *split_launches = ctx->qp_split_launches;
     return KITE_OK;
 }
 

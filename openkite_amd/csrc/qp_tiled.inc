@@ -55,7 +55,22 @@ __device__ unsigned long long g_qp_prof[24];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                             \
         QP_WSUB(ph);                                                                 \
     } while (0)
+// sums of a finished instance; `done` = 0 for a first phase that hands its kite
+// on (the resumed instance counts the kite and all its iterations)
+#define QP_PROF_FLUSH(done)                                                          \
+    do {                                                                             \
+        if (l == 0) {                                                                \
+            for (int i = 0; i < 9; ++i) atomicAdd(&g_qp_prof[i], prof_acc[i]);       \
+            if (done) {                                                              \
+                atomicAdd(&g_qp_prof[9], (unsigned long long)iters);                 \
+                atomicAdd(&g_qp_prof[10], 1ull);                                     \
+            }                                                                        \
+            for (int i = 0; i < 3; ++i) atomicAdd(&g_qp_prof[11 + i], prof_sub[i]);  \
+            for (int i = 0; i < 6; ++i) atomicAdd(&g_qp_prof[16 + i], prof_wsub[i]); \
+        }                                                                            \
+    } while (0)
 #else
+#define QP_PROF_FLUSH(done) do { } while (0)
 #define QP_MARK(ph) do { } while (0)
 #define QP_SUB(ph) do { } while (0)
 #define QP_WSUB(ph) do { } while (0)
@@ -365,7 +380,38 @@ __device__ __forceinline__ void tile_symv(const double4v* Ht, const double* w, d
     wave_sync();
 }
 
-template <bool LAZY>
+// Two-phase solve of the fast instance (MODE of qp_tiled_body<false, MODE>):
+//   QP_WHOLE   the solve in one launch
+//   QP_FIRST   the same up to the top of iteration QP_SPLIT_IT: a kite that
+//              passes the freeze test there (or earlier) finishes as in the
+//              whole solve; any other stores the state the loop carries across
+//              an iteration (checkpoint, below) and a dispatch key taken from
+//              its residual, and ends
+//   QP_RESUME  the constants of the solve as in the whole instance, the
+//              iterate from the checkpoint, the loop from it = QP_SPLIT_IT
+// The resumed kites are dispatched by their residual at the split, largest
+// first: a key from inside the solve predicts the remaining iterations, which
+// the previous step's count (k_qp_order on iters) barely does (DESIGN 4.3).
+// No operation changes or moves, so the result is bitwise the whole solve's.
+//
+// Checkpoint of kite b: QP_CK_SLOTS x 64 doubles at ckpt + b * QP_CK_DOUBLES,
+// slot-major (one coalesced store / load per slot):
+//   0..15  w, sl, su, zl, zu, rd, rpl, rpu (two slots each)
+//   16..21 slo, shi, zlo, zhi, rplo, rphi
+//   22     lane 0: mu, lane 1: rmax_prev, lane 2: resid (after residuals())
+// q.cw and a_prev are rewritten before they are read again.
+// Key of kite b: 0 when the first phase finished it, else 1 + the binary
+// exponent of resid clamped into [QP_KEY_EMIN, QP_KEY_EMIN + QP_KEY_BINS - 2].
+constexpr int QP_WHOLE = 0, QP_FIRST = 1, QP_RESUME = 2;
+#ifndef QP_SPLIT_IT
+#define QP_SPLIT_IT 9
+#endif
+constexpr int QP_CK_SLOTS = 23;
+constexpr int QP_CK_DOUBLES = QP_CK_SLOTS * 64;
+constexpr int QP_KEY_BINS = 64;        // keys 0 .. 63
+constexpr int QP_KEY_EMIN = -40;       // 2^-40 ~ 9e-13 < IPM_FREEZE: no live kite lies below
+
+template <bool LAZY, int MODE = QP_WHOLE>
 __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst C, int B,
                                                     const double* __restrict__ Htl,
                                                     const double* __restrict__ Habp,
@@ -377,7 +423,13 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
                                                     double* __restrict__ X, double* __restrict__ U,
                                                     double* __restrict__ u0_out, double* __restrict__ diag,
                                                     int32_t* __restrict__ status, double* __restrict__ kkt_out,
-                                                    int32_t* __restrict__ iters_out, int32_t* __restrict__ lazy, double* __restrict__ wstep) {
+                                                    int32_t* __restrict__ iters_out, int32_t* __restrict__ lazy, double* __restrict__ wstep,
+                                                    double* __restrict__ ckpt = nullptr,
+                                                    int32_t* __restrict__ key = nullptr) {
+    static_assert(!LAZY || MODE == QP_WHOLE, "the lazy instance is not split");
+    if constexpr (MODE == QP_RESUME) {
+        if (key[b] == 0) return;                       // finished by the first phase
+    }
     __shared__ double sT[QP_NTA * 16 * TLD];
     __shared__ double sP[(QP_NTA - 1) * 16 * TLD];
     __shared__ double sC[(QN + LAZY_ROWS) * QNC];   // vx-bound rows (kite controls only), then lazy rows
@@ -453,6 +505,13 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
     // next_round only, so the fast instance has none
     double lbv = 0.0, ubxv = 0.0;
     if constexpr (LAZY) { lbv = C.lbx[l < NX ? l : 0]; ubxv = C.ubx[l < NX ? l : 0]; }
+    // resume: the checkpoint, ahead of H (it is used first)
+    [[maybe_unused]] double ck[QP_CK_SLOTS];
+    if constexpr (MODE == QP_RESUME) {
+        const double* cp = ckpt + (size_t)b * QP_CK_DOUBLES + l;
+#pragma unroll
+        for (int v = 0; v < QP_CK_SLOTS; ++v) ck[v] = cp[v * 64];
+    }
     load_h();
     QP_WSUB(0);                                        // init: every load issued
 #pragma unroll
@@ -655,7 +714,21 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
         q.zhi = row_lane && TQ_HI ? IPM_Z0 : 0.0;
         wave_sync();
     };
-    init_rows();
+    [[maybe_unused]] double mu_ck = 0.0;
+    if constexpr (MODE == QP_RESUME) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            q.w[s] = ck[s]; q.sl[s] = ck[2 + s]; q.su[s] = ck[4 + s]; q.zl[s] = ck[6 + s]; q.zu[s] = ck[8 + s];
+            q.rd[s] = ck[10 + s]; q.rpl[s] = ck[12 + s]; q.rpu[s] = ck[14 + s];
+        }
+        q.slo = ck[16]; q.shi = ck[17]; q.zlo = ck[18]; q.zhi = ck[19]; q.rplo = ck[20]; q.rphi = ck[21];
+        q.cw = 0.0;                                    // rewritten by the next exact residuals before any use
+        mu_ck = uniform_d(readlane_d(ck[22], 0));
+        rmax_prev = uniform_d(readlane_d(ck[22], 1));
+        resid = uniform_d(readlane_d(ck[22], 2));
+    } else {
+        init_rows();
+    }
     QP_WSUB(1);                                        // init: small vectors consumed (first waits done)
     QP_WDRAIN(2);                                      // init: H arrived
 
@@ -839,13 +912,20 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
     }
     for (int round = LAZY ? 1 : 0; more; ++round) {
     iters = C.K;
-    for (int it = 0; it < C.K; ++it) {
+    [[maybe_unused]] const int kfirst = C.K > QP_SPLIT_IT ? QP_SPLIT_IT : C.K;   // the first phase's cap
+    for (int it = MODE == QP_RESUME ? QP_SPLIT_IT : 0; MODE == QP_FIRST ? it < kfirst : it < C.K; ++it) {
         // the lazy instance only re-solves with state-bound rows: exact residuals
         // there.  Such a re-solve starts far outside its new rows and can run into
         // the cap K; under the recursion the capped iterate then follows rounding
         // (the oracle's own plan moved by up to 3e-3 under a 1e-15 relative change
         // of its inputs, 1.7e-6 with exact residuals; tests/test_envelope.py)
-        const double mu = residuals(!LAZY && it > 0);
+        double mu_;
+        if constexpr (MODE == QP_RESUME) {             // the split iteration's residuals come from the checkpoint
+            if (it == QP_SPLIT_IT) mu_ = mu_ck; else mu_ = residuals(true);
+        } else {
+            mu_ = residuals(!LAZY && it > 0);
+        }
+        const double mu = mu_;
         QP_MARK(1);
         QP_WSTART();
         if (resid < IPM_FREEZE || resid != resid || mu < IPM_MU_FLOOR) { iters = it; break; }   // converged, poisoned or stalled
@@ -1016,6 +1096,41 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
         }
         QP_MARK(6);
     }
+    if constexpr (MODE == QP_FIRST) {
+        // the top of iteration QP_SPLIT_IT, outside the loop (an exit inside it
+        // costs the loop its register allocation): the whole solve's
+        // residuals and freeze test, then the hand-over
+        static_assert(QP_SPLIT_IT >= 1, "the split iteration may take the recursive residuals");
+        if (iters == C.K && C.K > QP_SPLIT_IT) {       // no exit before the split
+            const double mu = residuals(true);
+            QP_MARK(1);
+            if (resid < IPM_FREEZE || resid != resid || mu < IPM_MU_FLOOR) {
+                iters = QP_SPLIT_IT;
+            } else {
+        // (the addresses are formed here: hoisted out of the loop they
+        // would stay live through every iteration)
+        size_t off = (size_t)b * QP_CK_DOUBLES + l;
+        asm volatile("" : "+v"(off));
+        double* cp = ckpt + off;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            cp[s * 64] = q.w[s]; cp[(2 + s) * 64] = q.sl[s]; cp[(4 + s) * 64] = q.su[s];
+            cp[(6 + s) * 64] = q.zl[s]; cp[(8 + s) * 64] = q.zu[s];
+            cp[(10 + s) * 64] = q.rd[s]; cp[(12 + s) * 64] = q.rpl[s]; cp[(14 + s) * 64] = q.rpu[s];
+        }
+        cp[16 * 64] = q.slo; cp[17 * 64] = q.shi; cp[18 * 64] = q.zlo; cp[19 * 64] = q.zhi;
+        cp[20 * 64] = q.rplo; cp[21 * 64] = q.rphi;
+        cp[22 * 64] = l == 0 ? mu : (l == 1 ? rmax_prev : resid);
+        if (l == 0) {
+            int e = (int)((__double_as_longlong(resid) >> 52) & 0x7ff) - 1023;
+            e = e < QP_KEY_EMIN ? QP_KEY_EMIN : (e > QP_KEY_EMIN + QP_KEY_BINS - 2 ? QP_KEY_EMIN + QP_KEY_BINS - 2 : e);
+            key[b] = e - QP_KEY_EMIN + 1;
+        }
+        QP_PROF_FLUSH(0);
+        return;
+            }
+        }
+    }
     residuals(false);
     kkt = resid;
     QP_MARK(7);
@@ -1040,16 +1155,11 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
         if (l == 0) {
             if (kkt_out) kkt_out[b] = kkt;
             if (iters_out) iters_out[b] = iters;
+            if constexpr (MODE == QP_FIRST) key[b] = 0;       // finished: nothing to resume
         }
 #ifdef KITE_QP_PROF
         QP_MARK(8);
-        if (l == 0) {
-            for (int i = 0; i < 9; ++i) atomicAdd(&g_qp_prof[i], prof_acc[i]);
-            atomicAdd(&g_qp_prof[9], (unsigned long long)iters);
-            atomicAdd(&g_qp_prof[10], 1ull);
-            for (int i = 0; i < 3; ++i) atomicAdd(&g_qp_prof[11 + i], prof_sub[i]);
-            for (int i = 0; i < 6; ++i) atomicAdd(&g_qp_prof[16 + i], prof_wsub[i]);
-        }
+        QP_PROF_FLUSH(1);
 #endif
         return;
     }
@@ -1061,20 +1171,18 @@ __device__ __forceinline__ void qp_tiled_body(int b, ModelConst /*P*/, RtiConst 
 #undef TQ_HI
 #ifdef KITE_QP_PROF
     QP_MARK(8);
-    if (l == 0) {
-        for (int i = 0; i < 9; ++i) atomicAdd(&g_qp_prof[i], prof_acc[i]);
-        atomicAdd(&g_qp_prof[9], (unsigned long long)iters);
-        atomicAdd(&g_qp_prof[10], 1ull);
-        for (int i = 0; i < 3; ++i) atomicAdd(&g_qp_prof[11 + i], prof_sub[i]);
-        for (int i = 0; i < 6; ++i) atomicAdd(&g_qp_prof[16 + i], prof_wsub[i]);
-    }
+    QP_PROF_FLUSH(1);
 #endif
 }
 
 // the fast instance over the whole grid (LPT order); the lazy instance over
 // the kites the fast one listed (lazy[0] = count, lazy[1..]), grid-strided
 // (separate names: profilers that truncate template arguments keep them apart)
-__global__ __launch_bounds__(64, 1) void k_qp_tiled(ModelConst P, RtiConst C, int B,
+// k_qp_tiled_whole is the solve in one launch; k_qp_tiled the first phase of
+// the split solve (the name the profiling tools key on: it is the kernel of
+// the large batches they measure) and k_qp_tiled_resume its second phase over
+// the second order.
+__global__ __launch_bounds__(64, 1) void k_qp_tiled_whole(ModelConst P, RtiConst C, int B,
                                                     const double* __restrict__ Htl,
                                                     const double* __restrict__ Habp,
                                                     const double* __restrict__ Hbbp,
@@ -1088,7 +1196,41 @@ __global__ __launch_bounds__(64, 1) void k_qp_tiled(ModelConst P, RtiConst C, in
                                                     int32_t* __restrict__ iters_out,
                                                     const int32_t* __restrict__ order, int32_t* __restrict__ lazy,
                                                     double* __restrict__ wstep) {
-        qp_tiled_body<false>(order ? order[blockIdx.x] : blockIdx.x, P, C, B, Htl, Habp, Hbbp, hs, Cr, clp, cup, hmaxp, AB, DEF, X, U, u0_out, diag, status, kkt_out, iters_out, lazy, wstep);
+        qp_tiled_body<false, QP_WHOLE>(order ? order[blockIdx.x] : blockIdx.x, P, C, B, Htl, Habp, Hbbp, hs, Cr, clp, cup, hmaxp, AB, DEF, X, U, u0_out, diag, status, kkt_out, iters_out, lazy, wstep);
+}
+__global__ __launch_bounds__(64, 1) void k_qp_tiled(ModelConst P, RtiConst C, int B,
+                                                    const double* __restrict__ Htl,
+                                                    const double* __restrict__ Habp,
+                                                    const double* __restrict__ Hbbp,
+                                                    const double* __restrict__ hs, const double* __restrict__ Cr,
+                                                    const double* __restrict__ clp, const double* __restrict__ cup,
+                                                    const double* __restrict__ hmaxp,
+                                                    const double* __restrict__ AB, const double* __restrict__ DEF,
+                                                    double* __restrict__ X, double* __restrict__ U,
+                                                    double* __restrict__ u0_out, double* __restrict__ diag,
+                                                    int32_t* __restrict__ status, double* __restrict__ kkt_out,
+                                                    int32_t* __restrict__ iters_out,
+                                                    const int32_t* __restrict__ order, int32_t* __restrict__ lazy,
+                                                    double* __restrict__ wstep,
+                                                    double* __restrict__ ckpt, int32_t* __restrict__ key) {
+        qp_tiled_body<false, QP_FIRST>(order ? order[blockIdx.x] : blockIdx.x, P, C, B, Htl, Habp, Hbbp, hs, Cr, clp, cup, hmaxp, AB, DEF, X, U, u0_out, diag, status, kkt_out, iters_out, lazy, wstep, ckpt, key);
+}
+__global__ __launch_bounds__(64, 1) void k_qp_tiled_resume(ModelConst P, RtiConst C, int B,
+                                                    const double* __restrict__ Htl,
+                                                    const double* __restrict__ Habp,
+                                                    const double* __restrict__ Hbbp,
+                                                    const double* __restrict__ hs, const double* __restrict__ Cr,
+                                                    const double* __restrict__ clp, const double* __restrict__ cup,
+                                                    const double* __restrict__ hmaxp,
+                                                    const double* __restrict__ AB, const double* __restrict__ DEF,
+                                                    double* __restrict__ X, double* __restrict__ U,
+                                                    double* __restrict__ u0_out, double* __restrict__ diag,
+                                                    int32_t* __restrict__ status, double* __restrict__ kkt_out,
+                                                    int32_t* __restrict__ iters_out,
+                                                    const int32_t* __restrict__ order, int32_t* __restrict__ lazy,
+                                                    double* __restrict__ wstep,
+                                                    double* __restrict__ ckpt, int32_t* __restrict__ key) {
+        qp_tiled_body<false, QP_RESUME>(order[blockIdx.x], P, C, B, Htl, Habp, Hbbp, hs, Cr, clp, cup, hmaxp, AB, DEF, X, U, u0_out, diag, status, kkt_out, iters_out, lazy, wstep, ckpt, key);
 }
 __global__ __launch_bounds__(64, 1) void k_qp_tiled_lazy(ModelConst P, RtiConst C, int B,
                                                     const double* __restrict__ Htl,
@@ -1337,6 +1479,8 @@ __global__ __launch_bounds__(64) void k_expand20(RtiConst C, int B, const double
     }
 }
 
+size_t qp_split_ckpt_doubles() { return QP_CK_DOUBLES; }
+int qp_split_iteration() { return QP_SPLIT_IT; }
 bool qp_tiled_supported(const RtiConst& C) { return (C.N == 4 * QP_NTA || C.N == 40) && C.n == 4 * C.N + 2; }
 
 #include "qp_lds.inc"
@@ -1346,11 +1490,23 @@ hipError_t launch_qp_tiled(const ModelConst& P, const RtiConst& C, int B, const 
                            const double* cu, const double* hmax, const double* AB, const double* DEF, double* X,
                            double* U, double* u0, double* diag, int32_t* status, double* kkt, int32_t* iters,
                            const int32_t* order, int32_t* lazy, double* wstep, hipStream_t s,
-                           hipEvent_t after_main) {
+                           hipEvent_t after_main, const QpSplitBufs* split) {
     const int G = B < QP_LAZY_GRID ? B : QP_LAZY_GRID;
     if (C.N == 4 * QP_NTA) {
-        hipLaunchKernelGGL(k_qp_tiled, dim3(B), dim3(64), 0, s, P, C, B, Htl, Hab, Hbb, hs, Cr, cl, cu, hmax,
-                           AB, DEF, X, U, u0, diag, status, kkt, iters, order, lazy, wstep);
+        if (split) {
+            // first phase -> order of the kites still running by their residual -> second phase
+            hipLaunchKernelGGL(k_qp_tiled, dim3(B), dim3(64), 0, s, P, C, B, Htl, Hab, Hbb, hs, Cr, cl, cu,
+                               hmax, AB, DEF, X, U, u0, diag, status, kkt, iters, order, lazy, wstep, split->ckpt,
+                               split->key);
+            const hipError_t er = launch_qp_order_keys(B, QP_KEY_BINS - 1, split->key, split->order2, s);
+            if (er != hipSuccess) return er;
+            hipLaunchKernelGGL(k_qp_tiled_resume, dim3(B), dim3(64), 0, s, P, C, B, Htl, Hab, Hbb, hs, Cr, cl, cu,
+                               hmax, AB, DEF, X, U, u0, diag, status, kkt, iters, split->order2, lazy, wstep,
+                               split->ckpt, split->key);
+        } else {
+            hipLaunchKernelGGL(k_qp_tiled_whole, dim3(B), dim3(64), 0, s, P, C, B, Htl, Hab, Hbb, hs, Cr, cl, cu,
+                               hmax, AB, DEF, X, U, u0, diag, status, kkt, iters, order, lazy, wstep);
+        }
         if (after_main) { const hipError_t er = hipEventRecord(after_main, s); if (er != hipSuccess) return er; }
         hipLaunchKernelGGL(k_expand20, dim3((B + 3) / 4), dim3(64), 0, s, C, B, wstep, AB, DEF, X, U, u0, diag,
                            status, kkt, iters, iters ? iters + B : nullptr, lazy);

@@ -2280,11 +2280,15 @@ hipError_t launch_qp(const ModelConst& P, const RtiConst& C, int B, const double
 // The QP waves run 4 per SIMD in sequence at B = 4096; dispatching the long
 // ones first (largest-processing-time-first list scheduling) keeps the short
 // ones for the tail, where otherwise SIMDs idle while a late long kite ends.
+// The same sort orders the second phase of the split tiled QP by the key its
+// first phase wrote (K = the largest key; qp_tiled.inc): that call passes
+// clear = 0 and leaves both lists alone -- the prologue owns the cold one.
 __global__ __launch_bounds__(1024) void k_qp_order(int B, int K, const int32_t* __restrict__ iters,
-                                                   int32_t* __restrict__ order, int32_t* __restrict__ lazy) {
+                                                   int32_t* __restrict__ order, int32_t* __restrict__ lazy,
+                                                   int clear) {
     __shared__ int cnt[257];
     const int t = threadIdx.x;
-    if (t == 0) { lazy[0] = 0; lazy[B + 1] = 0; }     // and the prologue's cold list after it
+    if (clear && t == 0) { lazy[0] = 0; lazy[B + 1] = 0; }     // and the prologue's cold list after it
     const int nb = (K < 255 ? K : 255) + 1;
     for (int i = t; i <= nb; i += 1024) cnt[i] = 0;
     __syncthreads();
@@ -2339,7 +2343,11 @@ hipError_t launch_publish(int B, int N, const double* u0, const double* X, const
 }
 hipError_t launch_qp_order(const RtiConst& C, int B, const int32_t* iters, int32_t* order, int32_t* lazy,
                            hipStream_t s) {
-    hipLaunchKernelGGL(k_qp_order, dim3(1), dim3(1024), 0, s, B, C.K, iters, order, lazy);
+    hipLaunchKernelGGL(k_qp_order, dim3(1), dim3(1024), 0, s, B, C.K, iters, order, lazy, 1);
+    return hipGetLastError();
+}
+hipError_t launch_qp_order_keys(int B, int max_key, const int32_t* keys, int32_t* order, hipStream_t s) {
+    hipLaunchKernelGGL(k_qp_order, dim3(1), dim3(1024), 0, s, B, max_key, keys, order, (int32_t*)nullptr, 0);
     return hipGetLastError();
 }
 hipError_t launch_dynamics(const ModelConst& P, int count, const double* x, const double* u, double* f,

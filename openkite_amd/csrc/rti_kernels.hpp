@@ -112,12 +112,23 @@ hipError_t launch_condense(const RtiConst& C, int B, const double* X, const doub
                            double* hmax, int tiled, double* Htl, double* Hab, double* Hbb, hipStream_t s);
 // Tiled-QP path (N == 20): H_aa as 15 lower 16x16 C-layout tiles in lane order.
 bool qp_tiled_supported(const RtiConst& C);
+// split (N == 20 only, nullptr: the solve in one launch): the main solve in
+// two launches, the second dispatched by a key from inside the solve
+// (qp_tiled.inc).  ckpt: B x qp_split_ckpt_doubles() doubles, key and order2: B
+// words each.  after_main then follows the second launch.
+struct QpSplitBufs {
+    double* ckpt;
+    int32_t* key;
+    int32_t* order2;
+};
+size_t qp_split_ckpt_doubles();
+int qp_split_iteration();          // the build's QP_SPLIT_IT
 hipError_t launch_qp_tiled(const ModelConst& P, const RtiConst& C, int B, const double* Htl, const double* Hab,
                            const double* Hbb, const double* hs, const double* Cr, const double* cl,
                            const double* cu, const double* hmax, const double* AB, const double* DEF, double* X,
                            double* U, double* u0, double* diag, int32_t* status, double* kkt, int32_t* iters,
                            const int32_t* order, int32_t* lazy, double* wstep, hipStream_t s,
-                           hipEvent_t after_main = nullptr);
+                           hipEvent_t after_main = nullptr, const QpSplitBufs* split = nullptr);
 hipError_t launch_qp(const ModelConst& P, const RtiConst& C, int B, const double* Hs, const double* hs,
                      const double* Cr, const double* cl, const double* cu, const double* hmax,
                      const double* AB, const double* DEF, double* X, double* U, double* u0, double* diag,
@@ -131,6 +142,9 @@ hipError_t launch_publish(int B, int N, const double* u0, const double* X, const
                           int32_t* d_status, hipStream_t s);
 hipError_t launch_qp_order(const RtiConst& C, int B, const int32_t* iters, int32_t* order, int32_t* lazy,
                            hipStream_t s);
+// the same sort over keys in [0, max_key] (max_key <= 255), largest first,
+// without touching either list
+hipError_t launch_qp_order_keys(int B, int max_key, const int32_t* keys, int32_t* order, hipStream_t s);
 hipError_t launch_dynamics(const ModelConst& P, int count, const double* x, const double* u, double* f,
                            hipStream_t s);
 hipError_t launch_jacobian(const ModelConst& P, int count, const double* x, const double* u, double* Jx,

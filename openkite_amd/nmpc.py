@@ -31,6 +31,8 @@ IDENT_NAN, IDENT_CONVERGED, IDENT_AT_BOUND = 1, 2, 4   # KITE_IDENT_* (status wo
 IDENT_WIND_AT_BOUND = 8            # KITE_IDENT_WIND_AT_BOUND (joint identification: the wind ends on its box)
 IDENT_NPW = 24                     # KITE_IDENT_NPW: the 21 and the wind offset
 PARAMS_REJECTED = 1                # KITE_PARAMS_REJECTED (status word of set_params_device)
+QP_SPLIT_AUTO = -1                 # KITE_QP_SPLIT_*: the two-phase tiled QP (set_qp_split)
+QP_SPLIT_NEVER = 0
 EST_MODEL_CREATION = 0             # KITE_EST_MODEL_*: the model of the two EKFs (set_estimator_model)
 EST_MODEL_CONTROLLER = 1
 IDENT_NP = 21                      # KITE_IDENT_NP
@@ -268,6 +270,8 @@ _SIGNATURES = {
     "kite_nmpc_get_params": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "kite_nmpc_set_estimator_model": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "kite_nmpc_get_estimator_model": (ctypes.c_int, [ctypes.c_void_p, _IP]),
+    "kite_nmpc_set_qp_split": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "kite_nmpc_get_qp_split": (ctypes.c_int, [ctypes.c_void_p, _IP, _IP, _IP, ctypes.POINTER(ctypes.c_int64)]),
     "kite_ident_default_config": (None, [ctypes.POINTER(IdentConfig)]),
     "kite_ident_param_index": (ctypes.c_int, [ctypes.c_int32]),
     "kite_nmpc_ident_sens": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
@@ -919,6 +923,24 @@ class BatchNMPC:
         (``set_params[_device]``).  With a model per kite in force kite b
         filters with row b and a call's count must be the batch."""
         _check(lib().kite_nmpc_set_estimator_model(self._h, int(mode)), "set_estimator_model")
+
+    def set_qp_split(self, mode: int):
+        """The two-phase tiled QP at N = 20 (kite_nmpc_set_qp_split):
+        ``QP_SPLIT_AUTO`` (the default: split where several QP waves queue per
+        SIMD), ``QP_SPLIT_NEVER`` (one launch) or any positive value (split at
+        any batch).  The results are bitwise the same in every mode."""
+        _check(lib().kite_nmpc_set_qp_split(self._h, int(mode)), "set_qp_split")
+
+    def qp_split(self) -> dict:
+        """``mode`` set, whether the next step splits (``active``), the build's
+        ``split_iteration`` and the ``split_launches`` issued so far (a step
+        replayed from a captured graph counts once, at its capture)."""
+        m, a, k = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        n = ctypes.c_int64(0)
+        _check(lib().kite_nmpc_get_qp_split(self._h, ctypes.byref(m), ctypes.byref(a), ctypes.byref(k),
+                                            ctypes.byref(n)), "get_qp_split")
+        return dict(mode=int(m.value), active=bool(a.value), split_iteration=int(k.value),
+                    split_launches=int(n.value))
 
     @property
     def estimator_model(self) -> int:
