@@ -67,7 +67,10 @@ extern "C" {
                                       (kite_nmpc_identify_joint[_device],
                                       _ident_normal_joint, _ident_sens_joint,
                                       kite_ident_wind_config,
-                                      KITE_IDENT_WIND_AT_BOUND)                   */
+                                      KITE_IDENT_WIND_AT_BOUND) and the actuation
+                                      delay (kite_nmpc_plant_step_delayed[_device],
+                                      KITE_DELAY_*, KITE_PLANT_CMD_DROPPED,
+                                      KITE_PLANT_BAD_TAU)                         */
 #define KITE_PATH_MAX_HARMONICS 8 /* Fourier path: harmonics per axis              */
 
 /* ---- error codes ------------------------------------------------------ */
@@ -328,6 +331,59 @@ int kite_nmpc_plant_step(kite_nmpc_ctx* ctx, double* x13, const double* u4, doub
 /* Same on device pointers, asynchronous on the context stream.              */
 int kite_nmpc_plant_step_device(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4, double t0,
                                 double h, int32_t steps, int32_t substeps, int32_t* d_status);
+
+/* ---- actuation delay: a command line per kite ----------------------------
+ * The plant behind the reference's transport delay (src/nodes/
+ * transport_delay.cpp, a FIFO channel; simulator.cpp flies whatever command it
+ * received last).  Every kite owns a LINE of KITE_DELAY_NLINE doubles, kept by
+ * the caller: the control in force and a FIFO of at most KITE_DELAY_DEPTH
+ * pending commands with their arrival times.  An all-zero line is a reset:
+ * empty FIFO, zero control in force, no previous arrival.
+ *
+ * One call is one control period of `steps` plant steps of h, per kite:
+ *   send    u4_cmd[b] (if given) is sent at t_send = t0 with latency tau[b]:
+ *           t_arr = max(t_send, t_arr_prev) + tau[b], t_arr_prev the arrival of
+ *           the kite's last accepted command (t_send if there is none): the
+ *           channel never reorders.  tau[b] negative or non-finite: the
+ *           command is dropped, KITE_PLANT_BAD_TAU.  A send to a full line
+ *           drops the OLDEST pending command, KITE_PLANT_CMD_DROPPED.
+ *   fly     before plant step j (j = 0 .. steps-1) every pending command with
+ *           t_arr <= t_j leaves the FIFO in order and the last of them becomes
+ *           the control in force; t_j = t0 + (double)(j * substeps) * (h /
+ *           substeps), product rounded, then the sum.  The step then runs its
+ *           RK4 substeps as kite_nmpc_plant_step does.  Commands take effect at
+ *           plant ticks only; a step is never split.
+ *   report  u4_applied[b] is the control in force during the call's last plant
+ *           step; status[b] (written, not OR-ed) holds KITE_PLANT_* bits.  The
+ *           line advances whether or not the kite's state is finite.
+ *
+ * Line slots (doubles):                                                      */
+#define KITE_DELAY_DEPTH        4
+#define KITE_DELAY_NLINE        32   /* doubles per kite; all zero = reset */
+#define KITE_DELAY_COUNT        0    /* pending commands, 0 .. KITE_DELAY_DEPTH           */
+#define KITE_DELAY_T_PREV       1    /* arrival time of the last accepted command         */
+#define KITE_DELAY_HAS_PREV     2    /* 1 once a command has been accepted, else 0        */
+                                     /* 3: reserved, zero                                 */
+#define KITE_DELAY_U_FORCE      4    /* 4..7: the control in force (T, dE, dR, 4th)       */
+#define KITE_DELAY_T_ARR        8    /* 8..11: arrival times, slot 0 the oldest           */
+#define KITE_DELAY_U            12   /* 12..27: the pending commands, 4 doubles per slot  */
+                                     /* 28..31: reserved, zero; free slots are zero       */
+#define KITE_PLANT_CMD_DROPPED  2    /* plant status bit: a full line dropped its oldest command */
+#define KITE_PLANT_BAD_TAU      4    /* plant status bit: tau negative or non-finite, command dropped */
+
+/* x13, tau (B), line (B x KITE_DELAY_NLINE, in place), u4_applied (B x 4,
+ * nullable), status (B, nullable).  u4_cmd (B x 4) NULL: nothing is sent this
+ * period (tau may then be NULL).  The plant parameters, wind and gust are those
+ * of kite_nmpc_plant_set_params / _set_wind.  kite_nmpc_plant_step's argument
+ * checks, and line == NULL, or tau == NULL with a command: KITE_EINVAL, and
+ * nothing is changed.                                                        */
+int kite_nmpc_plant_step_delayed(kite_nmpc_ctx* ctx, double* x13, const double* u4_cmd, const double* tau,
+                                 double* line, double* u4_applied, double t0, double h, int32_t steps,
+                                 int32_t substeps, int32_t* status);
+/* Same on device pointers, asynchronous on the context stream.              */
+int kite_nmpc_plant_step_delayed_device(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4_cmd,
+                                        const double* d_tau, double* d_line, double* d_u4_applied, double t0,
+                                        double h, int32_t steps, int32_t substeps, int32_t* d_status);
 
 /* ---- introspection (tests, profiling) ---------------------------------- */
 /* ---- reference formulation: Chebyshev collocation (chebyshev.hpp) -------

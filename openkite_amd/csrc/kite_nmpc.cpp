@@ -1060,6 +1060,56 @@ int kite_nmpc_plant_step(kite_nmpc_ctx* ctx, double* x13, const double* u4, doub
                      });
 }
 
+// ---- actuation delay: the plant behind a per-kite command line ---------------
+extern "C++" {
+namespace {
+hipError_t plant_delay_launch(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4_cmd, const double* d_tau,
+                              double* d_line, double* d_u4_applied, double t0, double h, int32_t steps,
+                              int32_t substeps, int32_t* d_status, hipStream_t s) {
+    const ModelConst& P = ctx->plant_count == 1 ? ctx->plant_mc1 : ctx->mc;
+    return kite::launch_plant_delay(P, ctx->plant_count == ctx->B && ctx->plant_count > 1 ? ctx->plant_mc : nullptr,
+                                    ctx->B, ctx->plant_wind_mode, ctx->plant_wind, d_x13, d_u4_cmd, d_tau, d_line,
+                                    d_u4_applied, t0, h / substeps, steps, substeps, d_status, s);
+}
+}  // namespace
+}  // extern "C++"
+
+int kite_nmpc_plant_step_delayed_device(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4_cmd,
+                                        const double* d_tau, double* d_line, double* d_u4_applied, double t0,
+                                        double h, int32_t steps, int32_t substeps, int32_t* d_status) {
+    if (!ctx || !d_x13 || !d_line || (d_u4_cmd && !d_tau)) return KITE_EINVAL;
+    const int rc = plant_args_ok(t0, h, steps, substeps);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(plant_delay_launch(ctx, d_x13, d_u4_cmd, d_tau, d_line, d_u4_applied, t0, h, steps, substeps, d_status,
+                               ctx->stream));
+    return KITE_OK;
+}
+
+int kite_nmpc_plant_step_delayed(kite_nmpc_ctx* ctx, double* x13, const double* u4_cmd, const double* tau,
+                                 double* line, double* u4_applied, double t0, double h, int32_t steps,
+                                 int32_t substeps, int32_t* status) {
+    if (!ctx || !x13 || !line || (u4_cmd && !tau)) return KITE_EINVAL;
+    const int rc = plant_args_ok(t0, h, steps, substeps);
+    if (rc) return rc;
+    const size_t B = ctx->B;
+    // state and line are advanced in place in the staging buffer and copied out
+    // here, with the status words, ahead of run_items' synchronisation
+    return run_items(ctx, {{x13, B * 13}, {u4_cmd, B * 4}, {u4_cmd ? tau : nullptr, B}, {line, B * KITE_DELAY_NLINE}},
+                     {{u4_applied, B * 4}, {nullptr, (B + 1) / 2}},
+                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
+                         int32_t* dst = reinterpret_cast<int32_t*>(o[1]);
+                         hipError_t e = plant_delay_launch(ctx, i[0], u4_cmd ? i[1] : nullptr, u4_cmd ? i[2] : nullptr,
+                                                           i[3], o[0], t0, h, steps, substeps, dst, s);
+                         if (e != hipSuccess) return e;
+                         e = hipMemcpyAsync(x13, i[0], B * 13 * sizeof(double), hipMemcpyDeviceToHost, s);
+                         if (e != hipSuccess) return e;
+                         e = hipMemcpyAsync(line, i[3], B * KITE_DELAY_NLINE * sizeof(double), hipMemcpyDeviceToHost, s);
+                         if (e != hipSuccess || !status) return e;
+                         return hipMemcpyAsync(status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+                     });
+}
+
 // ---- Chebyshev collocation evaluator (chebyshev.hpp) ------------------------
 extern "C++" {
 namespace {

@@ -9,6 +9,7 @@
 //               [--ctrl-every K] [--sim-dt h] [--delay d] [--trace T] [--seed s]
 //               [--out file.jsonl] [--device i]
 //               [--plant-params file.csv] [--plant-wind file.csv]
+//               [--plant-delay SECONDS [--plant-delay-dev SECONDS] [--plant-delay-seed S]]
 //
 // --plant-params (B rows of the 52 kite_params values) and --plant-wind (B rows
 // of [W0 (3) | A (3) | f_hz | phase]) give every kite a plant of its own, which
@@ -17,6 +18,16 @@
 // step (K plant steps of sim-dt inside one kernel) and the summary line gains
 // "plant_nan", the kites whose plant state went non-finite on the way to this
 // step's measurement.
+//
+// --plant-delay puts every kite's plant behind a command line (the reference's
+// transport_delay node): u(t0) is sent at t0 and arrives after a latency drawn
+// per kite and step, uniform on [max(d - dev, 0), d + dev] (seeded), no sooner
+// than the command before it; the plant flies what has arrived, at its ticks.
+// The plant phase is then one kite_nmpc_plant_step_delayed call per control
+// step, with or without --plant-params / --plant-wind, and the summary line
+// gains "cmd_dropped", the kites whose full line dropped its oldest command in
+// the period before this step's measurement.  --delay is the controller's
+// assumption, --plant-delay is the plant's truth.
 //
 // Timeline (per control step, all kites in lockstep):
 //   measure x (13 plant states) -> kite_nmpc_step (prologue predicts over
@@ -42,14 +53,16 @@ struct Args {
     std::string x0_file, out_file, plant_params_file, plant_wind_file;
     int batch = 64, steps = 100, ctrl_every = 3, trace = 1, device = 0;
     double sim_dt = 0.02, delay = 0.1;
-    unsigned long long seed = 20261015ull;
+    double plant_delay = -1.0, plant_delay_dev = 0.0;      // < 0: no command line
+    unsigned long long seed = 20261015ull, plant_delay_seed = 0ull;
 };
 
 [[noreturn]] void usage(const char* argv0) {
     std::fprintf(stderr,
                  "usage: %s [--params yaml] [--batch B] [--steps S] [--x0 file.csv] [--ctrl-every K]\n"
                  "          [--sim-dt h] [--delay d] [--trace T] [--seed s] [--out file.jsonl] [--device i]\n"
-                 "          [--plant-params file.csv] [--plant-wind file.csv]\n",
+                 "          [--plant-params file.csv] [--plant-wind file.csv]\n"
+                 "          [--plant-delay seconds [--plant-delay-dev seconds] [--plant-delay-seed S]]\n",
                  argv0);
     std::exit(2);
 }
@@ -75,8 +88,12 @@ Args parse(int argc, char** argv) {
         else if (k == "--device") a.device = std::atoi(val());
         else if (k == "--plant-params") a.plant_params_file = val();
         else if (k == "--plant-wind") a.plant_wind_file = val();
+        else if (k == "--plant-delay") { a.plant_delay = std::atof(val()); if (!(a.plant_delay >= 0)) usage(argv[0]); }
+        else if (k == "--plant-delay-dev") a.plant_delay_dev = std::atof(val());
+        else if (k == "--plant-delay-seed") a.plant_delay_seed = std::strtoull(val(), nullptr, 10);
         else usage(argv[0]);
     }
+    if (!std::isfinite(a.plant_delay) || !(a.plant_delay_dev >= 0) || !std::isfinite(a.plant_delay_dev)) usage(argv[0]);
     if (a.batch < 1 || a.steps < 0 || a.ctrl_every < 1 || !(a.sim_dt > 0) || a.trace < 0) usage(argv[0]);
     return a;
 }
@@ -163,6 +180,17 @@ int main(int argc, char** argv) {
         if (rc) return fail("plant wind", rc);
     }
     std::vector<int32_t> plant_status(B, 0);
+    // a command line per kite (all zero: empty, zero control in force) and its latencies
+    const bool delayed = a.plant_delay >= 0.0;
+    std::vector<double> line, tau, u_applied;
+    std::mt19937_64 tau_rng(a.plant_delay_seed);
+    std::uniform_real_distribution<double> tau_dist(std::fmax(a.plant_delay - a.plant_delay_dev, 0.0),
+                                                    a.plant_delay + a.plant_delay_dev);
+    if (delayed) {
+        line.assign((size_t)B * KITE_DELAY_NLINE, 0.0);
+        tau.assign((size_t)B, a.plant_delay);
+        u_applied.assign((size_t)B * 4, 0.0);
+    }
 
     std::vector<double> plant;            // B x 13 plant states
     if (!a.x0_file.empty()) {
@@ -228,6 +256,11 @@ int main(int argc, char** argv) {
             for (int b = 0; b < B; ++b) n_pnan += (plant_status[b] & KITE_PLANT_NAN) != 0;
             std::fprintf(out, ", \"plant_nan\": %d", n_pnan);
         }
+        if (delayed) {
+            int n_drop = 0;
+            for (int b = 0; b < B; ++b) n_drop += (plant_status[b] & KITE_PLANT_CMD_DROPPED) != 0;
+            std::fprintf(out, ", \"cmd_dropped\": %d", n_drop);
+        }
         std::fprintf(out, "}\n");
         for (int b = 0; b < std::min(a.trace, B); ++b) {
             const double* ub = &u0[(size_t)b * 4];
@@ -246,6 +279,16 @@ int main(int argc, char** argv) {
         for (int b = 0; b < B; ++b) {
             std::memcpy(&u4[(size_t)b * 4], &u0[(size_t)b * 4], 3 * sizeof(double));
             u4[(size_t)b * 4 + 3] = 0.0;
+        }
+        if (delayed) {
+            // one launch for the whole control period: u(t0) goes down the line
+            if (a.plant_delay_dev > 0.0)
+                for (int b = 0; b < B; ++b) tau[b] = tau_dist(tau_rng);
+            rc = kite_nmpc_plant_step_delayed(ctx, plant.data(), u4.data(), tau.data(), line.data(), u_applied.data(), t,
+                                              a.sim_dt, a.ctrl_every, 4, plant_status.data());
+            if (rc) return fail("delayed plant", rc);
+            for (int k = 0; k < a.ctrl_every; ++k) t += a.sim_dt;
+            continue;
         }
         if (own_plant) {
             // one launch for the whole control period, from the time the step began

@@ -15,7 +15,8 @@
 // The integrator repeats rk4_primal (rti_kernels.hip) operation for operation
 // on the 13 kite states: the nominal plant (controller's constants, no wind)
 // is k_predict's arithmetic.  theta / thetadot are the controller's states,
-// not the plant's.
+// not the plant's.  k_plant_delay (below) is the same plant behind a command
+// line per kite: the reference's transport delay, still one launch per period.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -37,17 +38,52 @@ __device__ __forceinline__ double plant_time(double t0, int k, double hs) {
     return t0 + d;
 }
 
+// What stands between the command and the plant.  NoLine: nothing, the held
+// u4 flies (k_plant).  DelayLine: the kite's command line (k_plant_delay,
+// below): L its KITE_DELAY_NLINE doubles in memory, n the pending commands
+// after the send, head those that have left the FIFO in this call, flag the
+// send's KITE_PLANT_* bits.
+struct NoLine {
+    static constexpr bool kDelay = false;
+};
+struct DelayLine {
+    static constexpr bool kDelay = true;
+    double* L;
+    int n, head;
+    int32_t flag;
+};
+
+// a plant tick at time tj: every pending command with t_arr <= tj leaves the
+// FIFO in order, the last of them is the control in force from here on.  The
+// head's arrival time is re-read from the line (one load per tick)
+__device__ __forceinline__ void delay_arrivals(DelayLine& ln, double tj, double (&u)[NKU]) {
+    while (ln.head < ln.n && ln.L[KITE_DELAY_T_ARR + ln.head] <= tj) {
+#pragma unroll
+        for (int j = 0; j < NKU; ++j) u[j] = ln.L[KITE_DELAY_U + NU * ln.head + j];
+        ++ln.head;
+    }
+}
+
 // WIND: PLANT_CALM (the reference model: no sin, no wind arithmetic),
-// PLANT_WIND (constant W0) or PLANT_GUST; hs: the RK4 substep length
-template <int WIND>
+// PLANT_WIND (constant W0) or PLANT_GUST; hs: the RK4 substep length.
+// LINE: NoLine or DelayLine.  Both kernels share this one function, the RK4
+// substep with it; every line-specific statement sits under if constexpr, so
+// that k_plant's instances are the code they were before the line existed
+template <int WIND, class LINE>
 __device__ __forceinline__ void plant_lane(const ModelConst& P, int i, const double* __restrict__ wind8,
                                            double* __restrict__ x13, const double* __restrict__ u4, double t0,
-                                           double hs, int steps, int substeps, int32_t* __restrict__ status) {
+                                           double hs, int steps, int substeps, int32_t* __restrict__ status,
+                                           LINE& ln) {
     double x[NK], u[NKU];
 #pragma unroll
     for (int j = 0; j < NK; ++j) x[j] = x13[(size_t)i * NK + j];
+    if constexpr (LINE::kDelay) {
 #pragma unroll
-    for (int j = 0; j < NKU; ++j) u[j] = u4[(size_t)i * NU + j];
+        for (int j = 0; j < NKU; ++j) u[j] = ln.L[KITE_DELAY_U_FORCE + j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < NKU; ++j) u[j] = u4[(size_t)i * NU + j];
+    }
     bool fin = true;
 #pragma unroll
     for (int j = 0; j < NK; ++j) fin = fin && isfinite(x[j]);
@@ -70,6 +106,7 @@ __device__ __forceinline__ void plant_lane(const ModelConst& P, int i, const dou
         int k = 0;
         bool alive = true;
         for (int s = 0; s < steps && alive; ++s) {
+            if constexpr (LINE::kDelay) delay_arrivals(ln, plant_time(t0, k, hs), u);
             for (int m = 0; m < substeps; ++m, ++k) {
                 const double t = plant_time(t0, k, hs);
                 double xs[NK], acc[NK], kv[NK];
@@ -105,6 +142,7 @@ __device__ __forceinline__ void plant_lane(const ModelConst& P, int i, const dou
 #pragma unroll
         for (int j = 0; j < NK; ++j) x13[(size_t)i * NK + j] = x[j];
     }
+    if constexpr (LINE::kDelay) flag |= ln.flag;
     if (status) status[i] = flag;
 }
 
@@ -127,9 +165,11 @@ __global__ __launch_bounds__(64) void k_plant(ModelConst Pc, const double* __res
         for (int f = 0; f < kModelConstDoubles; ++f) pf[f] = mcf[(size_t)f * B + i];
         ModelConst P;
         __builtin_memcpy(&P, pf, sizeof(P));
-        plant_lane<WIND>(P, i, wind8, x13, u4, t0, hs, steps, substeps, status);
+        NoLine nl;
+        plant_lane<WIND>(P, i, wind8, x13, u4, t0, hs, steps, substeps, status, nl);
     } else {
-        plant_lane<WIND>(Pc, i, wind8, x13, u4, t0, hs, steps, substeps, status);
+        NoLine nl;
+        plant_lane<WIND>(Pc, i, wind8, x13, u4, t0, hs, steps, substeps, status, nl);
     }
 }
 
@@ -139,6 +179,158 @@ hipError_t launch_plant(const ModelConst& P, const double* mcf, int B, int wind_
     const dim3 grid((B + 63) / 64), block(64);
 #define KITE_PLANT_LAUNCH(PK, WM) \
     hipLaunchKernelGGL((k_plant<PK, WM>), grid, block, 0, s, P, mcf, B, wind8, x13, u4, t0, hs, steps, substeps, status)
+    if (mcf) {
+        if (wind_mode == PLANT_GUST) KITE_PLANT_LAUNCH(true, PLANT_GUST);
+        else if (wind_mode == PLANT_WIND) KITE_PLANT_LAUNCH(true, PLANT_WIND);
+        else KITE_PLANT_LAUNCH(true, PLANT_CALM);
+    } else {
+        if (wind_mode == PLANT_GUST) KITE_PLANT_LAUNCH(false, PLANT_GUST);
+        else if (wind_mode == PLANT_WIND) KITE_PLANT_LAUNCH(false, PLANT_WIND);
+        else KITE_PLANT_LAUNCH(false, PLANT_CALM);
+    }
+#undef KITE_PLANT_LAUNCH
+    return hipGetLastError();
+}
+
+// ---- the plant behind a command line (transport_delay.cpp, simulator.cpp) ----
+// Every kite owns a line of KITE_DELAY_NLINE doubles (kite_nmpc.h, KITE_DELAY_*):
+// the control in force and a FIFO of at most KITE_DELAY_DEPTH commands with
+// their arrival times.  One call is one control period: the command (if any) is
+// sent, then before every plant step the commands that have arrived leave the
+// FIFO in order and the last of them becomes the control in force.  The queue
+// logic does not look at the kite's state, so a frozen kite's line goes on.
+//
+// The FIFO stays in memory.  The lane appends the sent command to its own row,
+// re-reads the head's arrival time at each tick (one load, an L1/L2 hit; three
+// per launch at the driver's shape) and loads a command's three controls when it
+// arrives; the row is compacted at exit, when the RK4 registers are dead.  What
+// the flight loop carries beyond k_plant's registers is two counters.
+static_assert(KITE_DELAY_DEPTH == 4 && KITE_DELAY_NLINE == 32 && KITE_DELAY_U == KITE_DELAY_T_ARR + KITE_DELAY_DEPTH &&
+              KITE_DELAY_U + NU * KITE_DELAY_DEPTH <= KITE_DELAY_NLINE && NU == 4, "the line's layout");
+
+// the send: t_arr = max(t_send, t_arr_prev) + tau (the sequential sleep of
+// TDelay::publish: the channel never reorders); returns the pending count
+__device__ __forceinline__ int delay_send(double* L, const double* __restrict__ u_cmd, const double* __restrict__ tau,
+                                          int i, double t0, int32_t& flag) {
+    const double c = L[KITE_DELAY_COUNT];
+    int n = c >= 1.0 ? (c >= (double)KITE_DELAY_DEPTH ? KITE_DELAY_DEPTH : (int)c) : 0;   // NaN: 0
+    if (u_cmd) {
+        const double ta = tau[i];
+        if (!(ta >= 0.0) || !isfinite(ta)) {
+            flag |= KITE_PLANT_BAD_TAU;         // the command is dropped
+        } else {
+            const double prev = L[KITE_DELAY_HAS_PREV] != 0.0 ? L[KITE_DELAY_T_PREV] : t0;
+            const double t_arr = fmax(t0, prev) + ta;
+            if (n == KITE_DELAY_DEPTH) {        // full: the oldest goes (circular_buffer::push_back)
+                for (int s = 0; s + 1 < KITE_DELAY_DEPTH; ++s) {
+                    L[KITE_DELAY_T_ARR + s] = L[KITE_DELAY_T_ARR + s + 1];
+                    for (int q = 0; q < NU; ++q) L[KITE_DELAY_U + NU * s + q] = L[KITE_DELAY_U + NU * (s + 1) + q];
+                }
+                n = KITE_DELAY_DEPTH - 1;
+                flag |= KITE_PLANT_CMD_DROPPED;
+            }
+            L[KITE_DELAY_T_ARR + n] = t_arr;
+            for (int q = 0; q < NU; ++q) L[KITE_DELAY_U + NU * n + q] = u_cmd[(size_t)i * NU + q];
+            ++n;
+            L[KITE_DELAY_T_PREV] = t_arr;
+            L[KITE_DELAY_HAS_PREV] = 1.0;
+        }
+    }
+    return n;
+}
+
+// the line at the call's end.  What has left the FIFO by the last tick does
+// not depend on the flight (a frozen kite's line goes on): the pops the flight
+// did not get to are made up here.  Then the last arrival becomes the control
+// in force, the rest moves to the front and vacated slots are zeroed.  The
+// whole row comes into registers with one round of loads (the RK4 registers
+// are dead by now) and the new row is selected with compares, not indexed: a
+// chain of dependent loads and stores per slot costs more than the flight's
+// ticks together
+__device__ __forceinline__ void delay_finish(DelayLine& ln, double t_last, double* __restrict__ u_applied, int i) {
+    double* L = ln.L;
+    double ta[KITE_DELAY_DEPTH], uq[KITE_DELAY_DEPTH][NU], uf[NU];
+#pragma unroll
+    for (int s = 0; s < KITE_DELAY_DEPTH; ++s) {
+        ta[s] = L[KITE_DELAY_T_ARR + s];
+#pragma unroll
+        for (int q = 0; q < NU; ++q) uq[s][q] = L[KITE_DELAY_U + NU * s + q];
+    }
+#pragma unroll
+    for (int q = 0; q < NU; ++q) uf[q] = L[KITE_DELAY_U_FORCE + q];
+    const int n = ln.n;
+    int head = ln.head;
+#pragma unroll
+    for (int s = 0; s < KITE_DELAY_DEPTH; ++s)      // in order: slot s leaves only once every slot before it has
+        if (head == s && s < n && ta[s] <= t_last) head = s + 1;
+    ln.head = head;
+#pragma unroll
+    for (int s = 0; s < KITE_DELAY_DEPTH; ++s) {
+        if (head == s + 1) {
+#pragma unroll
+            for (int q = 0; q < NU; ++q) uf[q] = uq[s][q];
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < KITE_DELAY_DEPTH; ++s) {    // slot s <- slot s + head if that is pending, else zero
+        double t = 0.0, v[NU] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int src = s; src < KITE_DELAY_DEPTH; ++src) {
+            if (src - s == head && src < n) {
+                t = ta[src];
+#pragma unroll
+                for (int q = 0; q < NU; ++q) v[q] = uq[src][q];
+            }
+        }
+        L[KITE_DELAY_T_ARR + s] = t;
+#pragma unroll
+        for (int q = 0; q < NU; ++q) L[KITE_DELAY_U + NU * s + q] = v[q];
+    }
+    L[KITE_DELAY_COUNT] = (double)(n - head);
+#pragma unroll
+    for (int q = 0; q < NU; ++q) L[KITE_DELAY_U_FORCE + q] = uf[q];
+    if (u_applied) {
+#pragma unroll
+        for (int q = 0; q < NU; ++q) u_applied[(size_t)i * NU + q] = uf[q];
+    }
+}
+
+// k_plant's six variants behind the line; the send runs before the constants
+// are loaded, the flight as in k_plant
+template <bool PERKITE, int WIND>
+__global__ __launch_bounds__(64) void k_plant_delay(ModelConst Pc, const double* __restrict__ mcf, int B,
+                                                    const double* __restrict__ wind8, double* __restrict__ x13,
+                                                    const double* __restrict__ u_cmd, const double* __restrict__ tau,
+                                                    double* line, double* __restrict__ u_applied, double t0,
+                                                    double hs, int steps, int substeps, int32_t* __restrict__ status) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= B) return;
+    DelayLine ln;
+    ln.L = line + (size_t)i * KITE_DELAY_NLINE;
+    ln.head = 0;
+    ln.flag = 0;
+    ln.n = delay_send(ln.L, u_cmd, tau, i, t0, ln.flag);
+    const double t_last = plant_time(t0, (steps - 1) * substeps, hs);
+    if constexpr (PERKITE) {
+        double pf[kModelConstDoubles];
+#pragma unroll
+        for (int f = 0; f < kModelConstDoubles; ++f) pf[f] = mcf[(size_t)f * B + i];
+        ModelConst P;
+        __builtin_memcpy(&P, pf, sizeof(P));
+        plant_lane<WIND>(P, i, wind8, x13, nullptr, t0, hs, steps, substeps, status, ln);
+    } else {
+        plant_lane<WIND>(Pc, i, wind8, x13, nullptr, t0, hs, steps, substeps, status, ln);
+    }
+    delay_finish(ln, t_last, u_applied, i);
+}
+
+hipError_t launch_plant_delay(const ModelConst& P, const double* mcf, int B, int wind_mode, const double* wind8,
+                              double* x13, const double* u_cmd, const double* tau, double* line, double* u_applied,
+                              double t0, double hs, int steps, int substeps, int32_t* status, hipStream_t s) {
+    const dim3 grid((B + 63) / 64), block(64);
+#define KITE_PLANT_LAUNCH(PK, WM)                                                                               \
+    hipLaunchKernelGGL((k_plant_delay<PK, WM>), grid, block, 0, s, P, mcf, B, wind8, x13, u_cmd, tau, line, \
+                       u_applied, t0, hs, steps, substeps, status)
     if (mcf) {
         if (wind_mode == PLANT_GUST) KITE_PLANT_LAUNCH(true, PLANT_GUST);
         else if (wind_mode == PLANT_WIND) KITE_PLANT_LAUNCH(true, PLANT_WIND);

@@ -163,6 +163,11 @@ static_assert(sizeof(ModelConst) == kModelConstDoubles * sizeof(double), "ModelC
 hipError_t launch_plant(const ModelConst& P, const double* mcf, int B, int wind_mode, const double* wind8,
                         double* x13, const double* u4, double t0, double hs, int steps, int substeps,
                         int32_t* status, hipStream_t s);
+// the same plant behind a per-kite command line (k_plant_delay): line is B x
+// KITE_DELAY_NLINE; u_cmd (and then tau) and u_applied may be null
+hipError_t launch_plant_delay(const ModelConst& P, const double* mcf, int B, int wind_mode, const double* wind8,
+                              double* x13, const double* u_cmd, const double* tau, double* line, double* u_applied,
+                              double t0, double hs, int steps, int substeps, int32_t* status, hipStream_t s);
 hipError_t launch_rk4_sens_items(const ModelConst& P, int sens_fp32, int count, int M, double h, const double* x,
                                  const double* u, double* xo, double* A, double* Bm, double* X2, double* AB,
                                  double* DEF, hipStream_t s);

@@ -30,6 +30,12 @@ One step of a fleet of kites on one rank:
          over dt under u(t0) with the plant's own parameters, wind and gust
          (kite_nmpc_plant_step_device), and measures that state; theta and
          thetadot still come from the plan's node 1 (nmpf_node.cpp:220).
+         With ``GpuPlant(..., delay=ActuationDelay(...))`` u(t0) is sent down
+         a per-kite command line (transport_delay.cpp) and the kite flies what
+         has arrived (kite_nmpc_plant_step_delayed_device, still one launch);
+         the estimators propagate under that control, ``restart`` resets the
+         lines, and a ``recorder`` logs it (accepted only where it is constant
+         over a period: no jitter, a mean of whole periods).
 
   adapt  with ``recorder`` and ``adapt`` (an ``IdentConfig``): each time the
          flight log is full, before the RTI, every kite's 21 aerodynamic
@@ -157,7 +163,10 @@ class EpisodeScore:
     acc (B, 16) the accumulator rows (slots ``nmpc.SCORE_*``), mem (B, 8) what
     a period needs of the one before, ``first`` the flag of the period that
     starts an episode.  The accumulators persist across episodes: ``reset``
-    alone clears them.  Nothing here synchronises except ``summary``, which
+    alone clears them.  Behind a delayed plant (``ActuationDelay``) the loop
+    still scores the commanded u0 (control effort, control rate), not the
+    line's control in force; the tracking figures see the delay through the
+    true state.  Nothing here synchronises except ``summary``, which
     brings 16 doubles to the host."""
 
     def __init__(self, B: int, device=None):
@@ -206,20 +215,70 @@ class EpisodeScore:
         return out
 
 
+class ActuationDelay:
+    """The command line of every kite of a delayed plant (``GpuPlant(...,
+    delay=)``, kite_nmpc_plant_step_delayed_device) on the device: ``line`` (B,
+    DELAY_NLINE) the control in force and the FIFO of pending commands,
+    ``u_applied`` (B, 4) the control in force during the last plant step of the
+    last period, ``tau`` (B,) the latencies of the last send.  Each period
+    ``draw`` takes tau uniform on [max(mean - deviation, 0), mean + deviation]
+    (seconds; the reference's transport_delay node, there in ms) from a seeded
+    device generator; deviation == 0 draws nothing, tau is the mean.  A command
+    arrives at max(t_send, previous arrival) + tau: a mean above the control
+    period is a channel that falls behind and drops its oldest commands."""
+
+    def __init__(self, B: int, mean: float, deviation: float = 0.0, seed: int = 0, device=None):
+        from . import nmpc
+        if not (mean >= 0.0 and math.isfinite(mean)) or not (deviation >= 0.0 and math.isfinite(deviation)):
+            raise ValueError("ActuationDelay: mean and deviation are finite and >= 0")
+        f64 = dict(dtype=torch.float64, device=device)
+        self.B, self.mean, self.deviation, self.seed = int(B), float(mean), float(deviation), int(seed)
+        self.lo, self.hi = max(self.mean - self.deviation, 0.0), self.mean + self.deviation
+        self.line = torch.zeros((self.B, nmpc.DELAY_NLINE), **f64)
+        self.u_applied = torch.zeros((self.B, 4), **f64)
+        self.tau = torch.full((self.B,), self.lo, **f64)
+        self.gen = torch.Generator(device=self.line.device)
+        self.gen.manual_seed(self.seed)
+
+    def reset(self):
+        """Fresh lines (empty, zero control in force) and the generator back at its seed."""
+        self.line.zero_()
+        self.u_applied.zero_()
+        self.gen.manual_seed(self.seed)
+
+    def draw(self) -> torch.Tensor:
+        """The latencies of this period's send, (B,)."""
+        if self.hi > self.lo:
+            r = torch.rand((self.B,), generator=self.gen, dtype=torch.float64, device=self.line.device)
+            torch.add(r * (self.hi - self.lo), self.lo, out=self.tau)
+        return self.tau
+
+
 class GpuPlant:
     """The batched plant simulator of one C-ABI context on device tensors
     (kite_nmpc_plant_step_device: the context's plant parameters, wind and gust,
     see ``BatchNMPC.plant_set_params`` / ``plant_set_wind``): ``steps`` plant
-    steps of ``h`` per control period, RK4 with ``substeps`` each."""
+    steps of ``h`` per control period, RK4 with ``substeps`` each.  With
+    ``delay`` (an ``ActuationDelay``) the command goes through the kites' lines
+    and the period is the one delayed launch; None: the undelayed call."""
 
-    def __init__(self, ctx, h: float = 0.02, steps: int = 1, substeps: int = 4):
+    def __init__(self, ctx, h: float = 0.02, steps: int = 1, substeps: int = 4, delay=None):
         self.ctx, self.h, self.steps, self.substeps = ctx, float(h), int(steps), int(substeps)
+        self.delay = delay
 
     def advance(self, x13, u0, t0, status):
-        """x13 (B, 13) in place from t0 over steps * h under the held u0 (B, 4);
+        """x13 (B, 13) in place from t0 over steps * h under the held u0 (B, 4)
+        -- with a delay: u0 is sent at t0 and the line decides what flies;
         status (B,) int32 receives the KITE_PLANT_* words."""
-        self.ctx.plant_step_device(x13.data_ptr(), u0.data_ptr(), t0, self.h, self.steps, self.substeps,
-                                   status.data_ptr())
+        d = self.delay
+        if d is None:
+            self.ctx.plant_step_device(x13.data_ptr(), u0.data_ptr(), t0, self.h, self.steps, self.substeps,
+                                       status.data_ptr())
+            return
+        assert u0.is_contiguous() and x13.shape[0] == d.B
+        self.ctx.plant_step_delayed_device(x13.data_ptr(), u0.data_ptr(), d.draw().data_ptr(), d.line.data_ptr(), t0,
+                                           self.h, self.steps, self.substeps, d.u_applied.data_ptr(),
+                                           status.data_ptr())
 
 
 class FlightRecorder:
@@ -472,6 +531,19 @@ class FleetLoop:
             self.xp = x0[:, :13].clone().contiguous()
             self.t = 0.0
             self.plant_status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        # a delayed plant (``GpuPlant(..., delay=ActuationDelay)``): what flies is the
+        # line's control in force, not u0.  The estimators propagate under it.  A
+        # flight log holds one control per period, so it is kept only where the
+        # control is constant over each period: no jitter, a whole number of periods
+        self.delay = getattr(plant, "delay", None) if plant is not None else None
+        if self.delay is not None:
+            if self.delay.B != B:
+                raise ValueError(f"the delay holds {self.delay.B} lines, the loop flies {B} kites")
+            k = self.delay.mean / dt
+            if recorder is not None and (self.delay.deviation != 0.0 or abs(k - round(k)) > 1e-9 * max(1.0, k)):
+                raise ValueError("a recorder logs one control per period: with a delayed plant that is what flew "
+                                 "only when deviation == 0 and mean is a whole number of control periods "
+                                 f"(mean = {self.delay.mean}, deviation = {self.delay.deviation}, dt = {dt})")
         # a scorer (``EpisodeScore``): every period is scored right after the RTI,
         # one launch on the stream, from the true state at t0 and the control
         # just computed; None: no call is made
@@ -496,6 +568,8 @@ class FleetLoop:
             self.xp.copy_(self.x_init[:, :13])
             self.t = 0.0
             self.plant_status.zero_()
+        if self.delay is not None:
+            self.delay.reset()
         if self.ekf:
             self.xe.copy_(self.x_init[:, :13])
             self.P.copy_(self.P_init)
@@ -559,7 +633,7 @@ class FleetLoop:
             if self.wind_ekf_fresh:
                 self.wind_ekf_fresh = False
             else:
-                self.u3.copy_(self.u0[:, :3])
+                self.u3.copy_((self.u0 if self.delay is None else self.delay.u_applied)[:, :3])
                 self.stepper.wind_ekf(self.dt, self.ekf_substeps, self.xe, self.u3, self.P, self.z, self.W, self.V,
                                       self.ekf_status)
             self.stepper.set_wind_device(self.xe[:, 13:], self.wind_max)
@@ -576,8 +650,9 @@ class FleetLoop:
             self.x0[:, :13].copy_(self.xe)
         if self.ekf:
             # propagate under the control applied last (u(t0) of the previous
-            # plan), update with the measurement on the last substep
-            self.u3.copy_(self.u0[:, :3])
+            # plan; behind a delayed plant the line's control in force), update
+            # with the measurement on the last substep
+            self.u3.copy_((self.u0 if self.delay is None else self.delay.u_applied)[:, :3])
             h = self.dt / self.ekf_substeps
             for j in range(self.ekf_substeps):
                 self.stepper.ekf(h, self.xe, self.u3, self.P, self.z if j == self.ekf_substeps - 1 else None,
@@ -611,7 +686,8 @@ class FleetLoop:
                     self.recorder.record_wind(w.clamp(-self.wind_max, self.wind_max))
                 else:
                     self.recorder.record_wind(self.ident_wind)
-            self.recorder.record_control(self.u0)
+            if self.delay is None:
+                self.recorder.record_control(self.u0)
         if self.pub is not None:
             self.gathered = self.pub.publish(self.u0, self.diag)
         if self.plant is None:
@@ -620,6 +696,8 @@ class FleetLoop:
             # the kite flies on under u(t0); it is measured at t0 + dt, theta and
             # thetadot come from the plan (nmpf_node.cpp:220)
             self.plant.advance(self.xp, self.u0, self.t, self.plant_status)
+            if self.delay is not None and self.recorder is not None:
+                self.recorder.record_control(self.delay.u_applied)    # what flew this period
             self.t += self.dt
             self.x0[:, :13].copy_(self.xp)
             self.x0[:, 13:].copy_(self.traj[:, 1, 13:])

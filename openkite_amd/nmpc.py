@@ -24,6 +24,10 @@ KITE_OK, KITE_EINVAL, KITE_EHIP, KITE_ENOMEM, KITE_ENODEV, KITE_EIO, KITE_EPARSE
 ST_NAN, ST_QP_NOT_CONV, ST_MIN_SPEED, ST_STATE_BOUND, ST_THETA_WRAP, ST_STEP_REJECTED = 1, 2, 4, 8, 16, 32
 ST_RESTART = 64
 PLANT_NAN = 1                      # KITE_PLANT_NAN (plant status word)
+PLANT_CMD_DROPPED, PLANT_BAD_TAU = 2, 4    # KITE_PLANT_* of the delayed step: oldest command dropped, bad latency
+# the command line of plant_step_delayed (KITE_DELAY_*): depth, doubles per kite and the slots
+DELAY_DEPTH, DELAY_NLINE = 4, 32
+DELAY_COUNT, DELAY_T_PREV, DELAY_HAS_PREV, DELAY_U_FORCE, DELAY_T_ARR, DELAY_U = 0, 1, 2, 4, 8, 12
 EKF_NAN, EKF_S_NOT_PD = 1, 2       # KITE_EKF_* (status word of the wind-estimating and the kinematic EKF)
 EKF_INIT_BAD = 4                   # KITE_EKF_INIT_BAD (status word of kin_ekf_init)
 WIND_MAX_DEFAULT = 20.0            # set_wind_device: clamp of an estimated wind component, m/s
@@ -326,7 +330,13 @@ _SIGNATURES = {
     "kite_nmpc_plant_step_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_void_p]),
-    "kite_nmpc_closest_point_global": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP]),
+    "kite_nmpc_plant_step_delayed": (ctypes.c_int, [ctypes.c_void_p, _DP, _DP, _DP, _DP, _DP, ctypes.c_double,
+                                                    ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _IP]),
+    "kite_nmpc_plant_step_delayed_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                           ctypes.c_double, ctypes.c_double, ctypes.c_int32,
+                                                           ctypes.c_int32, ctypes.c_void_p]),
+    "kite_nmpc_closest_point_global": (ctypes.c_int,[ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP]),
     "kite_nmpc_closest_point_global_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                                              ctypes.c_void_p, ctypes.c_void_p]),
     "kite_nmpc_score_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _IP, _IP, ctypes.c_int32,
@@ -1011,6 +1021,49 @@ class BatchNMPC:
         v = lambda p: ctypes.c_void_p(p) if p else None
         _check(lib().kite_nmpc_plant_step_device(self._h, v(x13_ptr), v(u4_ptr), float(t0), float(h), int(steps),
                                                  int(substeps), v(status_ptr)), "plant_step_device")
+
+    def plant_step_delayed(self, x13, u4_cmd, tau, line, t0: float, h: float, steps: int = 1, substeps: int = 4):
+        """One control period of the plant behind the per-kite command line
+        (kite_nmpc_plant_step_delayed): u4_cmd (B, 4), or None to send nothing,
+        is sent at t0 with the latencies tau (B,); the commands that have
+        arrived take effect at the plant ticks.  line: (B, DELAY_NLINE), all
+        zero = a fresh line.  Returns (x13, line, u_applied, status): the new
+        state and line, the control in force during the last plant step and
+        the KITE_PLANT_* words (``PLANT_NAN``, ``PLANT_CMD_DROPPED``,
+        ``PLANT_BAD_TAU``)."""
+        B = self.batch
+        x, ln = _f64(x13), _f64(line)
+        if x.shape != (B, 13):
+            raise ValueError(f"x13: ({B}, 13) expected, got {x.shape}")
+        if ln.shape != (B, DELAY_NLINE):
+            raise ValueError(f"line: ({B}, {DELAY_NLINE}) expected, got {ln.shape}")
+        u = ta = None
+        if u4_cmd is not None:
+            u = _f64(u4_cmd)
+            if u.shape != (B, 4):
+                raise ValueError(f"u4_cmd: ({B}, 4) expected, got {u.shape}")
+            if tau is None:
+                raise ValueError("a command needs its latency: tau (B,)")
+            ta = _f64(tau)
+            if ta.shape != (B,):
+                raise ValueError(f"tau: ({B},) expected, got {ta.shape}")
+        x, ln = x.copy(), ln.copy()
+        ua = np.zeros((B, 4))
+        st = np.zeros(B, dtype=np.int32)
+        _check(lib().kite_nmpc_plant_step_delayed(self._h, _p(x), _p(u), _p(ta), _p(ln), _p(ua), float(t0), float(h),
+                                                  int(steps), int(substeps), st.ctypes.data_as(_IP)),
+               "plant_step_delayed")
+        return x, ln, ua, st
+
+    def plant_step_delayed_device(self, x13_ptr: int, u4_cmd_ptr: int, tau_ptr: int, line_ptr: int, t0: float,
+                                  h: float, steps: int = 1, substeps: int = 4, u4_applied_ptr: int = 0,
+                                  status_ptr: int = 0):
+        """plant_step_delayed in place on device pointers (asynchronous on the
+        context stream); u4_cmd_ptr 0: nothing is sent."""
+        v = lambda p: ctypes.c_void_p(p) if p else None
+        _check(lib().kite_nmpc_plant_step_delayed_device(self._h, v(x13_ptr), v(u4_cmd_ptr), v(tau_ptr), v(line_ptr),
+                                                         v(u4_applied_ptr), float(t0), float(h), int(steps),
+                                                         int(substeps), v(status_ptr)), "plant_step_delayed_device")
 
     # --- aerodynamic parameter identification ---------------------------------
     def _ident_rows(self, params, count: int) -> np.ndarray:
