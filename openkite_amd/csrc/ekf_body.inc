@@ -57,54 +57,17 @@
         __syncthreads();
         if (col) for (int i = 0; i < NK; ++i) sn[i * EKF_LD + j] = pcol[i];
         __syncthreads();
-        // S = P+[6:13, 6:13] + V, Cholesky in registers (lower, row-major packed)
+        // S = P+[6:13, 6:13] + V, Cholesky in registers (ekf_update.hpp); the
+        // pivots are not checked here
         double L[7][7];
-        for (int a = 0; a < 7; ++a)
-            for (int c = 0; c <= a; ++c) L[a][c] = kite ? sn[(6 + a) * EKF_LD + 6 + c] + V[a * 7 + c] : (a == c);
-        for (int c = 0; c < 7; ++c) {
-            double d = L[c][c];
-            for (int k = 0; k < c; ++k) d -= L[c][k] * L[c][k];
-            d = sqrt(d);
-            L[c][c] = d;
-            for (int a = c + 1; a < 7; ++a) {
-                double t = L[a][c];
-                for (int k = 0; k < c; ++k) t -= L[a][k] * L[c][k];
-                L[a][c] = t / d;
-            }
-        }
-        auto solve = [&](double r[7]) {          // r <- S^-1 r
-            for (int a = 0; a < 7; ++a) {
-                double t = r[a];
-                for (int k = 0; k < a; ++k) t -= L[a][k] * r[k];
-                r[a] = t / L[a][a];
-            }
-            for (int a = 6; a >= 0; --a) {
-                double t = r[a];
-                for (int k = a + 1; k < 7; ++k) t -= L[k][a] * r[k];
-                r[a] = t / L[a][a];
-            }
-        };
+        ekf_chol7<EKF_LD>(sn, V, kite, L);
         // P[:, j] = P+[:, j] - P+[:, 6:13] S^-1 P+[6:13, j]
-        if (col) {
-            double c7[7];
-            for (int a = 0; a < 7; ++a) c7[a] = pcol[6 + a];
-            solve(c7);
-            for (int i = 0; i < NK; ++i) {
-                double t = pcol[i];
-                for (int a = 0; a < 7; ++a) t = fma(-sn[i * EKF_LD + 6 + a], c7[a], t);
-                pcol[i] = t;
-            }
-        }
+        if (col) ekf_cov_update<NK, EKF_LD>(sn, L, pcol, pcol);
         // x = x+ + P+[:, 6:13] S^-1 (z - x+[6:13])
         if (kite && j == 0) {
             double y[7];
             for (int a = 0; a < 7; ++a) y[a] = z[(size_t)b * 7 + a] - xn[6 + a];
-            solve(y);
-            for (int i = 0; i < NK; ++i) {
-                double t = xn[i];
-                for (int a = 0; a < 7; ++a) t = fma(sn[i * EKF_LD + 6 + a], y[a], t);
-                xn[i] = t;
-            }
+            ekf_state_update<NK, EKF_LD>(sn, L, xn, y, xn);
         }
     }
     if (col)

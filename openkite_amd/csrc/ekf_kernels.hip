@@ -13,9 +13,13 @@
 // A P A' from the matrices shared through LDS (13 x 14 per kite, LDS
 // broadcast reads); the 7 x 7 innovation covariance is factored per lane in
 // registers.  HBM per kite: x, u, z, P in and x, P out = 2 x 1.4 KB.
+// The update (Cholesky, solves, the two gain products) is ekf_update.hpp's,
+// shared with k_ekf_wind and k_ekf_kin; this filter does not check the pivots
+// and does not symmetrise P.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "ekf_update.hpp"
 #include "kite_model.hpp"
 #include "rti_kernels.hpp"
 

@@ -11,7 +11,8 @@
 //   [with z]        z_q <- -z_q if z_q . q_est < 0 (q and -q are one attitude)
 //   per substep s of h = dt / substeps
 //     A = I_13 + J(x) h,  x <- one RK4 step over h,  P <- A P A' + W
-//   then, with a measurement z, one update as k_ekf_wind does it:
+//   then, with a measurement z, one update (ekf_update.hpp, shared with
+//   k_ekf and k_ekf_wind) and its containment tail (ekf_commit, there):
 //     S = P[6:13, 6:13] + V (7 x 7 Cholesky in registers),
 //     x <- x + P[:, 6:13] S^-1 (z - x[6:13]),  P <- P - P[:, 6:13] S^-1 P[6:13, :]
 //     P <- (P + P') / 2
@@ -21,7 +22,7 @@
 //     the reference's CVODES integrates over a fixed 0.02 s whatever the
 //     filter's dt is (kite.cpp:656-659 against kiteEKF.cpp:83-93);
 //   * the measured quaternion is sign-aligned to the estimate (above);
-//   * P is symmetrised after the update (k_ekf_wind's reason).
+//   * P is symmetrised after the update (ekf_commit, ekf_update.hpp, has the reason).
 //
 // Lane layout: the neighbours' -- 16 lanes per kite, 4 kites per wavefront,
 // 64-thread blocks; lane j < 13 owns column j of P, lanes 13..15 carry zeros.
@@ -42,7 +43,7 @@
 // 32 lanes, 64 banks) meets two kites 208 = 6 x 32 + 16 doubles apart, whose
 // columns 0..12 fall on banks 0..25 and 32..57: no conflicts.
 //
-// Containment: k_ekf_wind's.  The four kites of a block share every barrier.
+// Containment: the four kites of a block share every barrier.
 // No lane returns early and no loop is left early; a frozen or out-of-range
 // kite is predicated.  A kite whose estimate or covariance is non-finite on
 // entry, or turns non-finite in a substep, keeps its last finite x and P
@@ -53,6 +54,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "ekf_update.hpp"
 #include "kin_model.hpp"
 #include "kite_nmpc/kite_nmpc.h"
 #include "rti_kernels.hpp"
@@ -63,12 +65,6 @@ constexpr int KEKF_T = 64;             // threads per block = 4 kites x 16 lanes
 constexpr int KEKF_N = 13;             // filter states
 constexpr int KEKF_LD = 16;            // LDS row stride of the 13 x 13 matrix
 constexpr int KEKF_KS = 13 * 16;       // LDS kite stride
-
-// true when any of the calling kite's 16 lanes passes bad (kk: kite of the wave)
-__device__ __forceinline__ bool kin_kite_any(bool bad, int kk) {
-    const unsigned long long m = __ballot(bad);
-    return ((m >> (kk * 16)) & 0xFFFFull) != 0;
-}
 
 __global__ __launch_bounds__(KEKF_T) void k_ekf_kin(int count, double dt, int substeps, double* __restrict__ x,
                                                     double* __restrict__ Pc, const double* __restrict__ z,
@@ -91,7 +87,7 @@ __global__ __launch_bounds__(KEKF_T) void k_ekf_kin(int count, double dt, int su
 
     bool fin = true;
     for (int i = 0; i < KEKF_N; ++i) fin = fin && isfinite(xv[i]) && isfinite(pcol[i]);
-    bool alive = !kin_kite_any(!fin, kk);     // uniform over the kite's lanes
+    bool alive = !kite_any(!fin, kk);     // uniform over the kite's lanes
     const bool entry_ok = alive;
     int32_t flag = alive ? 0 : KITE_EKF_NAN;
 
@@ -171,7 +167,7 @@ __global__ __launch_bounds__(KEKF_T) void k_ekf_kin(int count, double dt, int su
         bool ok = true;
         for (int i = 6; i < KEKF_N; ++i) ok = ok && isfinite(xn[i]);
         for (int i = 0; i < KEKF_N; ++i) ok = ok && isfinite(pn[i]);
-        const bool bad = kin_kite_any(!ok, kk);
+        const bool bad = kite_any(!ok, kk);
         if (alive && bad) { alive = false; flag = KITE_EKF_NAN; }   // keeps the last finite x, P
         if (alive) {
             for (int i = 6; i < KEKF_N; ++i) xv[i] = xn[i];
@@ -183,74 +179,14 @@ __global__ __launch_bounds__(KEKF_T) void k_ekf_kin(int count, double dt, int su
     if (z) {                                 // uniform over the grid
         for (int i = 0; i < KEKF_N; ++i) sp[i * KEKF_LD + j] = pcol[i];
         __syncthreads();
-        // S = P+[6:13, 6:13] + V, Cholesky in registers (lower), every lane its own copy
+        // the pose update and its containment tail: ekf_update.hpp
         double L[7][7];
-        for (int a = 0; a < 7; ++a)
-            for (int c = 0; c <= a; ++c) L[a][c] = kite ? sp[(6 + a) * KEKF_LD + 6 + c] + V[a * 7 + c] : (a == c);
-        bool pd = zfin;                      // a non-finite measurement is a bad update
-        for (int c = 0; c < 7; ++c) {
-            double d = L[c][c];
-            for (int k = 0; k < c; ++k) d -= L[c][k] * L[c][k];
-            pd = pd && (d > 0.0) && isfinite(d);
-            d = sqrt(d);
-            L[c][c] = d;
-            for (int a = c + 1; a < 7; ++a) {
-                double t = L[a][c];
-                for (int k = 0; k < c; ++k) t -= L[a][k] * L[c][k];
-                L[a][c] = t / d;
-            }
-        }
-        auto solve = [&](double r[7]) {          // r <- S^-1 r
-            for (int a = 0; a < 7; ++a) {
-                double t = r[a];
-                for (int k = 0; k < a; ++k) t -= L[a][k] * r[k];
-                r[a] = t / L[a][a];
-            }
-            for (int a = 6; a >= 0; --a) {
-                double t = r[a];
-                for (int k = a + 1; k < 7; ++k) t -= L[k][a] * r[k];
-                r[a] = t / L[a][a];
-            }
-        };
-        // P[:, j] = P+[:, j] - P+[:, 6:13] S^-1 P+[6:13, j]
-        double pu[KEKF_N], xu[KEKF_N];
-        {
-            double c7[7];
-            for (int a = 0; a < 7; ++a) c7[a] = pcol[6 + a];
-            solve(c7);
-            for (int i = 0; i < KEKF_N; ++i) {
-                double t = pcol[i];
-                for (int a = 0; a < 7; ++a) t = fma(-sp[i * KEKF_LD + 6 + a], c7[a], t);
-                pu[i] = t;
-            }
-        }
-        // x = x+ + P+[:, 6:13] S^-1 (z - x+[6:13])
-        {
-            double y[7];
-            for (int a = 0; a < 7; ++a) y[a] = zv[a] - xv[6 + a];
-            solve(y);
-            for (int i = 0; i < KEKF_N; ++i) {
-                double t = xv[i];
-                for (int a = 0; a < 7; ++a) t = fma(sp[i * KEKF_LD + 6 + a], y[a], t);
-                xu[i] = t;
-            }
-        }
-        bool ok = true;
-        for (int i = 0; i < KEKF_N; ++i) ok = ok && isfinite(pu[i]) && isfinite(xu[i]);
-        const bool bad = kin_kite_any(!ok, kk);
-        if (alive && !pd) flag |= KITE_EKF_S_NOT_PD;            // update skipped
-        else if (alive && bad) flag |= KITE_EKF_NAN;            // keeps the propagated estimate
-        const bool updated = alive && pd && !bad;
-        if (updated) {
-            for (int i = 0; i < KEKF_N; ++i) { pcol[i] = pu[i]; xv[i] = xu[i]; }
-        }
-        // P <- (P + P') / 2 of an updated kite (windekf_body.inc has the reason).
-        // Both halves of a pair add the same two numbers, so P leaves exactly symmetric.
-        __syncthreads();                     // every lane is done with P+ in sp
-        for (int i = 0; i < KEKF_N; ++i) sp[i * KEKF_LD + j] = pcol[i];
-        __syncthreads();
-        if (updated)
-            for (int i = 0; i < KEKF_N; ++i) pcol[i] = 0.5 * (pcol[i] + sp[jc * KEKF_LD + i]);
+        const bool pd = ekf_chol7<KEKF_LD>(sp, V, kite, L) && zfin;   // a non-finite measurement is a bad update
+        double pu[KEKF_N], xu[KEKF_N], y[7];
+        ekf_cov_update<KEKF_N, KEKF_LD>(sp, L, pcol, pu);
+        for (int a = 0; a < 7; ++a) y[a] = zv[a] - xv[6 + a];
+        ekf_state_update<KEKF_N, KEKF_LD>(sp, L, xv, y, xu);
+        ekf_commit<KEKF_N, KEKF_LD>(sp, j, jc, kk, alive, pd, pu, xu, pcol, xv, flag);
     }
     // a kite that was non-finite on entry is left untouched; one frozen in a
     // substep stores the last finite x and P it holds

@@ -24,6 +24,7 @@
 #include "kite_model_dp.hpp"
 #include "rti_kernels.hpp"
 #include "score_kernels.hpp"
+#include "stage_layout.hpp"
 
 using kite::ModelConst;
 using kite::RtiConst;
@@ -888,40 +889,44 @@ int kite_nmpc_set_solution(kite_nmpc_ctx* ctx, const double* traj, const double*
 // ---- model-level entry points: host in/out, scratch on device -------------
 extern "C++" {
 namespace {
+namespace ks = kite_stage;
+
+inline int32_t* i32(double* p) { return reinterpret_cast<int32_t*>(p); }
+
+// Stage the segments in the context's scratch (stage_layout.hpp), copy the
+// inputs in, launch(d, stream) with d[i] the device address of segment i
+// (nullptr for an input the caller did not pass), copy the outputs out,
+// synchronise once.
 template <class Launch>
-int run_items(kite_nmpc_ctx* ctx, const std::vector<std::pair<const double*, size_t>>& in,
-              const std::vector<std::pair<double*, size_t>>& out, Launch launch) {
+int run_items(kite_nmpc_ctx* ctx, const std::vector<ks::Seg>& segs, Launch launch) {
     HIP_TRY(hipSetDevice(ctx->device));
-    size_t total = 0;
-    for (auto& p : in) total += p.second;
-    for (auto& p : out) total += p.second;
-    int rc = ensure_scratch(ctx, total * sizeof(double));
+    const ks::Layout L = ks::layout(segs);
+    int rc = ensure_scratch(ctx, L.total * sizeof(double));
     if (rc) return rc;
-    std::vector<double*> din, dout;
-    double* cur = ctx->scratch;
     hipStream_t s = ctx->stream;
-    for (auto& p : in) {
-        din.push_back(cur);
-        if (p.first) HIP_TRY(hipMemcpyAsync(cur, p.first, p.second * sizeof(double), hipMemcpyHostToDevice, s));
-        cur += p.second;
+    std::vector<double*> d(segs.size());
+    for (size_t i = 0; i < segs.size(); ++i) {
+        d[i] = ks::absent(segs[i]) ? nullptr : ctx->scratch + L.off[i];
+        if (ks::copies_in(segs[i]))
+            HIP_TRY(hipMemcpyAsync(d[i], segs[i].host, ks::bytes(segs[i]), hipMemcpyHostToDevice, s));
     }
-    for (auto& p : out) { dout.push_back(cur); cur += p.second; }
-    HIP_TRY(launch(din, dout, s));
-    for (size_t i = 0; i < out.size(); ++i)
-        if (out[i].first)
-            HIP_TRY(hipMemcpyAsync(out[i].first, dout[i], out[i].second * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(launch(d, s));
+    for (size_t i = 0; i < segs.size(); ++i)
+        if (ks::copies_out(segs[i]))
+            HIP_TRY(hipMemcpyAsync(segs[i].host, d[i], ks::bytes(segs[i]), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return KITE_OK;
 }
+
 }  // namespace
 }  // extern "C++"
 
 int kite_nmpc_dynamics(kite_nmpc_ctx* ctx, int32_t count, const double* x15, const double* u4, double* f15) {
     if (!ctx || count < 1 || !x15 || !u4 || !f15) return KITE_EINVAL;
     const size_t c = count;
-    return run_items(ctx, {{x15, c * 15}, {u4, c * 4}}, {{f15, c * 15}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_dynamics(ctx->mc, count, i[0], i[1], o[0], s);
+    return run_items(ctx, {ks::in(x15, c * 15), ks::in(u4, c * 4), ks::out(f15, c * 15)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_dynamics(ctx->mc, count, d[0], d[1], d[2], s);
                      });
 }
 
@@ -929,9 +934,9 @@ int kite_nmpc_jacobian(kite_nmpc_ctx* ctx, int32_t count, const double* x13, con
                        double* Ju) {
     if (!ctx || count < 1 || !x13 || !u3 || !Jx || !Ju) return KITE_EINVAL;
     const size_t c = count;
-    return run_items(ctx, {{x13, c * 13}, {u3, c * 3}}, {{Jx, c * 169}, {Ju, c * 39}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_jacobian(ctx->mc, count, i[0], i[1], o[0], o[1], s);
+    return run_items(ctx, {ks::in(x13, c * 13), ks::in(u3, c * 3), ks::out(Jx, c * 169), ks::out(Ju, c * 39)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_jacobian(ctx->mc, count, d[0], d[1], d[2], d[3], s);
                      });
 }
 
@@ -940,9 +945,9 @@ int kite_nmpc_predict(kite_nmpc_ctx* ctx, int32_t count, const double* x15, cons
     if (!ctx || count < 1 || !x15 || !u4 || !x15_out || steps < 1 || !std::isfinite(tf)) return KITE_EINVAL;
     const size_t c = count;
     const double h = tf / steps;
-    return run_items(ctx, {{x15, c * 15}, {u4, c * 4}}, {{x15_out, c * 15}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_predict(ctx->mc, count, i[0], i[1], h, steps, o[0], s);
+    return run_items(ctx, {ks::in(x15, c * 15), ks::in(u4, c * 4), ks::out(x15_out, c * 15)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_predict(ctx->mc, count, d[0], d[1], h, steps, d[2], s);
                      });
 }
 
@@ -968,6 +973,19 @@ int plant_args_ok(double t0, double h, int32_t steps, int32_t substeps) {
     if (!(h > 0.0) || !std::isfinite(h) || !std::isfinite(t0) || steps < 1 || substeps < 1) return KITE_EINVAL;
     if ((int64_t)steps * substeps > (int64_t)1 << 24) return KITE_EINVAL;
     return KITE_OK;
+}
+
+// the checks of kite_nmpc_plant_step / _delayed and their _device twins (pointers of either side)
+int plant_check(const kite_nmpc_ctx* ctx, const double* x13, const double* u4, double t0, double h, int32_t steps,
+                int32_t substeps) {
+    if (!ctx || !x13 || !u4) return KITE_EINVAL;
+    return plant_args_ok(t0, h, steps, substeps);
+}
+
+int plant_delay_check(const kite_nmpc_ctx* ctx, const double* x13, const double* u4_cmd, const double* tau,
+                      const double* line, double t0, double h, int32_t steps, int32_t substeps) {
+    if (!ctx || !x13 || !line || (u4_cmd && !tau)) return KITE_EINVAL;
+    return plant_args_ok(t0, h, steps, substeps);
 }
 
 hipError_t plant_launch(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4, double t0, double h, int32_t steps,
@@ -1032,8 +1050,7 @@ int kite_nmpc_plant_set_wind(kite_nmpc_ctx* ctx, const double* wind8) {
 
 int kite_nmpc_plant_step_device(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4, double t0, double h,
                                 int32_t steps, int32_t substeps, int32_t* d_status) {
-    if (!ctx || !d_x13 || !d_u4) return KITE_EINVAL;
-    const int rc = plant_args_ok(t0, h, steps, substeps);
+    const int rc = plant_check(ctx, d_x13, d_u4, t0, h, steps, substeps);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(plant_launch(ctx, d_x13, d_u4, t0, h, steps, substeps, d_status, ctx->stream));
@@ -1042,21 +1059,12 @@ int kite_nmpc_plant_step_device(kite_nmpc_ctx* ctx, double* d_x13, const double*
 
 int kite_nmpc_plant_step(kite_nmpc_ctx* ctx, double* x13, const double* u4, double t0, double h, int32_t steps,
                          int32_t substeps, int32_t* status) {
-    if (!ctx || !x13 || !u4) return KITE_EINVAL;
-    const int rc = plant_args_ok(t0, h, steps, substeps);
+    const int rc = plant_check(ctx, x13, u4, t0, h, steps, substeps);
     if (rc) return rc;
     const size_t B = ctx->B;
-    // the state is advanced in place in the staging buffer; the status words
-    // (int32) sit in a scratch output and are copied out here, ahead of
-    // run_items' synchronisation
-    return run_items(ctx, {{x13, B * 13}, {u4, B * 4}}, {{nullptr, (B + 1) / 2}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         int32_t* dst = reinterpret_cast<int32_t*>(o[0]);
-                         hipError_t e = plant_launch(ctx, i[0], i[1], t0, h, steps, substeps, dst, s);
-                         if (e != hipSuccess) return e;
-                         e = hipMemcpyAsync(x13, i[0], B * 13 * sizeof(double), hipMemcpyDeviceToHost, s);
-                         if (e != hipSuccess || !status) return e;
-                         return hipMemcpyAsync(status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    return run_items(ctx, {ks::inout(x13, B * 13), ks::in(u4, B * 4), ks::out(status, B)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return plant_launch(ctx, d[0], d[1], t0, h, steps, substeps, i32(d[2]), s);
                      });
 }
 
@@ -1077,8 +1085,7 @@ hipError_t plant_delay_launch(kite_nmpc_ctx* ctx, double* d_x13, const double* d
 int kite_nmpc_plant_step_delayed_device(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4_cmd,
                                         const double* d_tau, double* d_line, double* d_u4_applied, double t0,
                                         double h, int32_t steps, int32_t substeps, int32_t* d_status) {
-    if (!ctx || !d_x13 || !d_line || (d_u4_cmd && !d_tau)) return KITE_EINVAL;
-    const int rc = plant_args_ok(t0, h, steps, substeps);
+    const int rc = plant_delay_check(ctx, d_x13, d_u4_cmd, d_tau, d_line, t0, h, steps, substeps);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(plant_delay_launch(ctx, d_x13, d_u4_cmd, d_tau, d_line, d_u4_applied, t0, h, steps, substeps, d_status,
@@ -1089,24 +1096,16 @@ int kite_nmpc_plant_step_delayed_device(kite_nmpc_ctx* ctx, double* d_x13, const
 int kite_nmpc_plant_step_delayed(kite_nmpc_ctx* ctx, double* x13, const double* u4_cmd, const double* tau,
                                  double* line, double* u4_applied, double t0, double h, int32_t steps,
                                  int32_t substeps, int32_t* status) {
-    if (!ctx || !x13 || !line || (u4_cmd && !tau)) return KITE_EINVAL;
-    const int rc = plant_args_ok(t0, h, steps, substeps);
+    const int rc = plant_delay_check(ctx, x13, u4_cmd, tau, line, t0, h, steps, substeps);
     if (rc) return rc;
     const size_t B = ctx->B;
-    // state and line are advanced in place in the staging buffer and copied out
-    // here, with the status words, ahead of run_items' synchronisation
-    return run_items(ctx, {{x13, B * 13}, {u4_cmd, B * 4}, {u4_cmd ? tau : nullptr, B}, {line, B * KITE_DELAY_NLINE}},
-                     {{u4_applied, B * 4}, {nullptr, (B + 1) / 2}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         int32_t* dst = reinterpret_cast<int32_t*>(o[1]);
-                         hipError_t e = plant_delay_launch(ctx, i[0], u4_cmd ? i[1] : nullptr, u4_cmd ? i[2] : nullptr,
-                                                           i[3], o[0], t0, h, steps, substeps, dst, s);
-                         if (e != hipSuccess) return e;
-                         e = hipMemcpyAsync(x13, i[0], B * 13 * sizeof(double), hipMemcpyDeviceToHost, s);
-                         if (e != hipSuccess) return e;
-                         e = hipMemcpyAsync(line, i[3], B * KITE_DELAY_NLINE * sizeof(double), hipMemcpyDeviceToHost, s);
-                         if (e != hipSuccess || !status) return e;
-                         return hipMemcpyAsync(status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    // without a command its latencies are not sent either
+    return run_items(ctx,
+                     {ks::inout(x13, B * 13), ks::in(u4_cmd, B * 4), ks::in(u4_cmd ? tau : nullptr, B),
+                      ks::inout(line, B * KITE_DELAY_NLINE), ks::out(u4_applied, B * 4), ks::out(status, B)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return plant_delay_launch(ctx, d[0], d[1], d[2], d[3], d[4], t0, h, steps, substeps,
+                                                   i32(d[5]), s);
                      });
 }
 
@@ -1259,6 +1258,18 @@ int estimator_model(const kite_nmpc_ctx* ctx, int32_t count, const ModelConst** 
     }
     return KITE_OK;
 }
+
+struct EstModel {
+    const ModelConst* mc;
+    const double* mct;
+};
+
+// the checks of kite_nmpc_ekf_step and its _device twin (pointers of either side)
+int ekf_check(const kite_nmpc_ctx* ctx, int32_t count, double dt, const double* x13, const double* u3,
+              const double* P169, const double* z7, const double* W169, const double* V49, EstModel* m) {
+    if (!ctx || count < 1 || !x13 || !u3 || !P169 || !W169 || (z7 && !V49) || !std::isfinite(dt)) return KITE_EINVAL;
+    return estimator_model(ctx, count, &m->mc, &m->mct);
+}
 }  // namespace
 }  // extern "C++"
 
@@ -1300,40 +1311,26 @@ int kite_nmpc_get_estimator_model(kite_nmpc_ctx* ctx, int32_t* mode) {
 
 int kite_nmpc_ekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, double* d_x13, const double* d_u3,
                               double* d_P169, const double* d_z7, const double* d_W169, const double* d_V49) {
-    if (!ctx || count < 1 || !d_x13 || !d_u3 || !d_P169 || !d_W169 || (d_z7 && !d_V49) || !std::isfinite(dt))
-        return KITE_EINVAL;
-    const ModelConst* mc;
-    const double* mct;
-    { const int rc = estimator_model(ctx, count, &mc, &mct); if (rc) return rc; }
+    EstModel m;
+    const int rc = ekf_check(ctx, count, dt, d_x13, d_u3, d_P169, d_z7, d_W169, d_V49, &m);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(kite::launch_ekf(*mc, mct, count, dt, d_x13, d_u3, d_P169, d_z7, d_W169, d_V49, ctx->stream));
+    HIP_TRY(kite::launch_ekf(*m.mc, m.mct, count, dt, d_x13, d_u3, d_P169, d_z7, d_W169, d_V49, ctx->stream));
     return KITE_OK;
 }
 
 int kite_nmpc_ekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, double* x13, const double* u3, double* P169,
                        const double* z7, const double* W169, const double* V49) {
-    if (!ctx || count < 1 || !x13 || !u3 || !P169 || !W169 || (z7 && !V49) || !std::isfinite(dt)) return KITE_EINVAL;
-    const ModelConst* mc;
-    const double* mct;
-    { const int rc = estimator_model(ctx, count, &mc, &mct); if (rc) return rc; }
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t c = count;
-    const size_t nx = c * 13, nu = c * 3, np = c * 169, nz = z7 ? c * 7 : 0;
-    int rc = ensure_scratch(ctx, (nx + nu + np + nz + 169 + 49) * sizeof(double));
+    EstModel m;
+    const int rc = ekf_check(ctx, count, dt, x13, u3, P169, z7, W169, V49, &m);
     if (rc) return rc;
-    double *dx = ctx->scratch, *du = dx + nx, *dP = du + nu, *dz = dP + np, *dW = dz + nz, *dV = dW + 169;
-    hipStream_t s = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(dx, x13, nx * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(du, u3, nu * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dP, P169, np * sizeof(double), hipMemcpyHostToDevice, s));
-    if (z7) HIP_TRY(hipMemcpyAsync(dz, z7, nz * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dW, W169, 169 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (V49) HIP_TRY(hipMemcpyAsync(dV, V49, 49 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(kite::launch_ekf(*mc, mct, count, dt, dx, du, dP, z7 ? dz : nullptr, dW, dV, s));
-    HIP_TRY(hipMemcpyAsync(x13, dx, nx * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(P169, dP, np * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return KITE_OK;
+    const size_t c = count;
+    return run_items(ctx,
+                     {ks::inout(x13, c * 13), ks::in(u3, c * 3), ks::inout(P169, c * 169), ks::in(z7, z7 ? c * 7 : 0),
+                      ks::in(W169, 169), ks::in(V49, 49)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_ekf(*m.mc, m.mct, count, dt, d[0], d[1], d[2], d[3], d[4], d[5], s);
+                     });
 }
 
 // ---- wind-estimating EKF (windekf_kernels.hip) ------------------------------
@@ -1364,62 +1361,53 @@ int windekf_args_ok(int32_t count, double dt, int32_t substeps) {
     if (substeps < 1 || substeps > (1 << 24)) return KITE_EINVAL;
     return KITE_OK;
 }
+
+// the checks of kite_nmpc_windekf_step and its _device twin (pointers of either side)
+int windekf_check(const kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, const double* x16,
+                  const double* u3, const double* P256, const double* z7, const double* W256, const double* V49,
+                  EstModel* m) {
+    if (!ctx || !x16 || !u3 || !P256 || !W256 || (z7 && !V49)) return KITE_EINVAL;
+    const int rc = windekf_args_ok(count, dt, substeps);
+    return rc ? rc : estimator_model(ctx, count, &m->mc, &m->mct);
+}
 }  // namespace
 }  // extern "C++"
 
 int kite_nmpc_windekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, double* d_x16,
                                   const double* d_u3, double* d_P256, const double* d_z7, const double* d_W256,
                                   const double* d_V49, int32_t* d_status) {
-    if (!ctx || !d_x16 || !d_u3 || !d_P256 || !d_W256 || (d_z7 && !d_V49)) return KITE_EINVAL;
-    const int rc = windekf_args_ok(count, dt, substeps);
+    EstModel m;
+    const int rc = windekf_check(ctx, count, dt, substeps, d_x16, d_u3, d_P256, d_z7, d_W256, d_V49, &m);
     if (rc) return rc;
-    const ModelConst* mc;
-    const double* mct;
-    { const int rcm = estimator_model(ctx, count, &mc, &mct); if (rcm) return rcm; }
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(kite::launch_ekf_wind(*mc, mct, count, dt, substeps, d_x16, d_u3, d_P256, d_z7, d_W256, d_V49, d_status,
-                                  ctx->stream));
+    HIP_TRY(kite::launch_ekf_wind(*m.mc, m.mct, count, dt, substeps, d_x16, d_u3, d_P256, d_z7, d_W256, d_V49,
+                                  d_status, ctx->stream));
     return KITE_OK;
 }
 
 int kite_nmpc_windekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, double* x16,
                            const double* u3, double* P256, const double* z7, const double* W256, const double* V49,
                            int32_t* status) {
-    if (!ctx || !x16 || !u3 || !P256 || !W256 || (z7 && !V49)) return KITE_EINVAL;
-    const int rc0 = windekf_args_ok(count, dt, substeps);
-    if (rc0) return rc0;
-    const ModelConst* mc;
-    const double* mct;
-    { const int rcm = estimator_model(ctx, count, &mc, &mct); if (rcm) return rcm; }
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t c = count;
-    const size_t nx = c * 16, nu = c * 3, np = c * 256, nz = z7 ? c * 7 : 0, ns = (c + 1) / 2;
-    int rc = ensure_scratch(ctx, (nx + nu + np + nz + 256 + 49 + ns) * sizeof(double));
+    EstModel m;
+    const int rc = windekf_check(ctx, count, dt, substeps, x16, u3, P256, z7, W256, V49, &m);
     if (rc) return rc;
-    double *dx = ctx->scratch, *du = dx + nx, *dP = du + nu, *dz = dP + np, *dW = dz + nz, *dV = dW + 256;
-    int32_t* dst = reinterpret_cast<int32_t*>(dV + 49);
-    hipStream_t s = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(dx, x16, nx * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(du, u3, nu * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dP, P256, np * sizeof(double), hipMemcpyHostToDevice, s));
-    if (z7) HIP_TRY(hipMemcpyAsync(dz, z7, nz * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dW, W256, 256 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (V49) HIP_TRY(hipMemcpyAsync(dV, V49, 49 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(kite::launch_ekf_wind(*mc, mct, count, dt, substeps, dx, du, dP, z7 ? dz : nullptr, dW, dV, dst, s));
-    HIP_TRY(hipMemcpyAsync(x16, dx, nx * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(P256, dP, np * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return KITE_OK;
+    const size_t c = count;
+    return run_items(ctx,
+                     {ks::inout(x16, c * 16), ks::in(u3, c * 3), ks::inout(P256, c * 256), ks::in(z7, z7 ? c * 7 : 0),
+                      ks::in(W256, 256), ks::in(V49, 49), ks::out(status, c)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_ekf_wind(*m.mc, m.mct, count, dt, substeps, d[0], d[1], d[2], d[3], d[4],
+                                                      d[5], i32(d[6]), s);
+                     });
 }
 
 int kite_nmpc_jacobian_wind(kite_nmpc_ctx* ctx, int32_t count, const double* x13, const double* u3, const double* w3,
                             double* J) {
     if (!ctx || count < 1 || !x13 || !u3 || !w3 || !J) return KITE_EINVAL;
     const size_t c = count;
-    return run_items(ctx, {{x13, c * 13}, {u3, c * 3}, {w3, c * 3}}, {{J, c * 13 * 16}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_jacobian_wind(ctx->mc, count, i[0], i[1], i[2], o[0], s);
+    return run_items(ctx, {ks::in(x13, c * 13), ks::in(u3, c * 3), ks::in(w3, c * 3), ks::out(J, c * 13 * 16)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_jacobian_wind(ctx->mc, count, d[0], d[1], d[2], d[3], s);
                      });
 }
 
@@ -1463,18 +1451,33 @@ int pose_frame_arg(const kite_pose_frame* frame, kite::PoseFrame* F, const kite:
     *use = F;
     return KITE_OK;
 }
+
+// the checks of kite_nmpc_kinekf_step / kite_nmpc_kinekf_init and their
+// _device twins (pointers of either side)
+int kinekf_check(const kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, const double* x13,
+                 const double* P169, const double* z7, const double* W169, const double* V49,
+                 const kite_pose_frame* frame, kite::PoseFrame* F, const kite::PoseFrame** use) {
+    if (!ctx || !x13 || !P169 || !W169 || (z7 && !V49)) return KITE_EINVAL;
+    const int rc = windekf_args_ok(count, dt, substeps);
+    return rc ? rc : pose_frame_arg(frame, F, use);
+}
+
+int kinekf_init_check(const kite_nmpc_ctx* ctx, int32_t count, const double* pose_prev7, const double* pose_new7,
+                      const double* x13_out, const kite_pose_frame* frame, kite::PoseFrame* F,
+                      const kite::PoseFrame** use) {
+    if (!ctx || count < 1 || !pose_prev7 || !pose_new7 || !x13_out) return KITE_EINVAL;
+    return pose_frame_arg(frame, F, use);
+}
 }  // namespace
 }  // extern "C++"
 
 int kite_nmpc_kinekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, double* d_x13,
                                  double* d_P169, const double* d_z7, const double* d_W169, const double* d_V49,
                                  const kite_pose_frame* frame, int32_t* d_status) {
-    if (!ctx || !d_x13 || !d_P169 || !d_W169 || (d_z7 && !d_V49)) return KITE_EINVAL;
-    const int rc = windekf_args_ok(count, dt, substeps);
-    if (rc) return rc;
     kite::PoseFrame F;
     const kite::PoseFrame* use;
-    { const int rcf = pose_frame_arg(frame, &F, &use); if (rcf) return rcf; }
+    const int rc = kinekf_check(ctx, count, dt, substeps, d_x13, d_P169, d_z7, d_W169, d_V49, frame, &F, &use);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(kite::launch_ekf_kin(count, dt, substeps, d_x13, d_P169, d_z7, d_W169, d_V49, use, d_status,
                                  ctx->stream));
@@ -1484,40 +1487,27 @@ int kite_nmpc_kinekf_step_device(kite_nmpc_ctx* ctx, int32_t count, double dt, i
 int kite_nmpc_kinekf_step(kite_nmpc_ctx* ctx, int32_t count, double dt, int32_t substeps, double* x13, double* P169,
                           const double* z7, const double* W169, const double* V49, const kite_pose_frame* frame,
                           int32_t* status) {
-    if (!ctx || !x13 || !P169 || !W169 || (z7 && !V49)) return KITE_EINVAL;
-    const int rc0 = windekf_args_ok(count, dt, substeps);
-    if (rc0) return rc0;
     kite::PoseFrame F;
     const kite::PoseFrame* use;
-    { const int rcf = pose_frame_arg(frame, &F, &use); if (rcf) return rcf; }
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t c = count;
-    const size_t nx = c * 13, np = c * 169, nz = z7 ? c * 7 : 0, ns = (c + 1) / 2;
-    int rc = ensure_scratch(ctx, (nx + np + nz + 169 + 49 + ns) * sizeof(double));
+    const int rc = kinekf_check(ctx, count, dt, substeps, x13, P169, z7, W169, V49, frame, &F, &use);
     if (rc) return rc;
-    double *dx = ctx->scratch, *dP = dx + nx, *dz = dP + np, *dW = dz + nz, *dV = dW + 169;
-    int32_t* dst = reinterpret_cast<int32_t*>(dV + 49);
-    hipStream_t s = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(dx, x13, nx * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dP, P169, np * sizeof(double), hipMemcpyHostToDevice, s));
-    if (z7) HIP_TRY(hipMemcpyAsync(dz, z7, nz * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dW, W169, 169 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (V49) HIP_TRY(hipMemcpyAsync(dV, V49, 49 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(kite::launch_ekf_kin(count, dt, substeps, dx, dP, z7 ? dz : nullptr, dW, dV, use, dst, s));
-    HIP_TRY(hipMemcpyAsync(x13, dx, nx * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(P169, dP, np * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return KITE_OK;
+    const size_t c = count;
+    return run_items(ctx,
+                     {ks::inout(x13, c * 13), ks::inout(P169, c * 169), ks::in(z7, z7 ? c * 7 : 0), ks::in(W169, 169),
+                      ks::in(V49, 49), ks::out(status, c)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_ekf_kin(count, dt, substeps, d[0], d[1], d[2], d[3], d[4], use,
+                                                     i32(d[5]), s);
+                     });
 }
 
 int kite_nmpc_kinekf_init_device(kite_nmpc_ctx* ctx, int32_t count, double dt, const double* d_pose_prev7,
                                  const double* d_pose_new7, const kite_pose_frame* frame, double* d_x13_out,
                                  int32_t* d_status) {
-    if (!ctx || count < 1 || !d_pose_prev7 || !d_pose_new7 || !d_x13_out) return KITE_EINVAL;
     kite::PoseFrame F;
     const kite::PoseFrame* use;
-    { const int rcf = pose_frame_arg(frame, &F, &use); if (rcf) return rcf; }
+    const int rc = kinekf_init_check(ctx, count, d_pose_prev7, d_pose_new7, d_x13_out, frame, &F, &use);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(kite::launch_ekf_kin_init(count, dt, d_pose_prev7, d_pose_new7, use, d_x13_out, d_status, ctx->stream));
     return KITE_OK;
@@ -1525,35 +1515,25 @@ int kite_nmpc_kinekf_init_device(kite_nmpc_ctx* ctx, int32_t count, double dt, c
 
 int kite_nmpc_kinekf_init(kite_nmpc_ctx* ctx, int32_t count, double dt, const double* pose_prev7,
                           const double* pose_new7, const kite_pose_frame* frame, double* x13_out, int32_t* status) {
-    if (!ctx || count < 1 || !pose_prev7 || !pose_new7 || !x13_out) return KITE_EINVAL;
     kite::PoseFrame F;
     const kite::PoseFrame* use;
-    { const int rcf = pose_frame_arg(frame, &F, &use); if (rcf) return rcf; }
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t c = count;
-    const size_t nz = c * 7, nx = c * 13, ns = (c + 1) / 2;
-    int rc = ensure_scratch(ctx, (2 * nz + nx + ns) * sizeof(double));
+    const int rc = kinekf_init_check(ctx, count, pose_prev7, pose_new7, x13_out, frame, &F, &use);
     if (rc) return rc;
-    double *dp = ctx->scratch, *dn = dp + nz, *dx = dn + nz;
-    int32_t* dst = reinterpret_cast<int32_t*>(dx + nx);
-    hipStream_t s = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(dp, pose_prev7, nz * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dn, pose_new7, nz * sizeof(double), hipMemcpyHostToDevice, s));
-    // a kite that cannot be initialised keeps the caller's x13
-    HIP_TRY(hipMemcpyAsync(dx, x13_out, nx * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(kite::launch_ekf_kin_init(count, dt, dp, dn, use, dx, dst, s));
-    HIP_TRY(hipMemcpyAsync(x13_out, dx, nx * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return KITE_OK;
+    const size_t c = count;
+    // x13_out goes in as well: a kite that cannot be initialised keeps the caller's x13
+    return run_items(ctx, {ks::in(pose_prev7, c * 7), ks::in(pose_new7, c * 7), ks::inout(x13_out, c * 13),
+                           ks::out(status, c)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_ekf_kin_init(count, dt, d[0], d[1], use, d[2], i32(d[3]), s);
+                     });
 }
 
 int kite_nmpc_jacobian_kin(kite_nmpc_ctx* ctx, int32_t count, const double* x13, double* J169) {
     if (!ctx || count < 1 || !x13 || !J169) return KITE_EINVAL;
     const size_t c = count;
-    return run_items(ctx, {{x13, c * 13}}, {{J169, c * 169}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_jacobian_kin(count, i[0], o[0], s);
+    return run_items(ctx, {ks::in(x13, c * 13), ks::out(J169, c * 169)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_jacobian_kin(count, d[0], d[1], s);
                      });
 }
 
@@ -1749,12 +1729,12 @@ int kite_nmpc_ident_sens_wind(kite_nmpc_ctx* ctx, int32_t count, double h, int32
     if (rc) return rc;
     const size_t c = count;
     return run_items(ctx,
-                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {x13, c * 13}, {u3, c * 3},
-                      {w3, w3 ? c * 3 : 0}},
-                     {{x13_out, c * 13}, {S, c * 13 * KITE_IDENT_NP}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_ident_sens(count, nparams, h / substeps, substeps, i[0], i[1], i[2],
-                                                        w3 ? i[3] : nullptr, o[0], o[1], s);
+                     {ks::in(reinterpret_cast<const double*>(params), (size_t)nparams * 52), ks::in(x13, c * 13),
+                      ks::in(u3, c * 3), ks::in(w3, w3 ? c * 3 : 0), ks::out(x13_out, c * 13),
+                      ks::out(S, c * 13 * KITE_IDENT_NP)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_ident_sens(count, nparams, h / substeps, substeps, d[0], d[1], d[2],
+                                                        d[3], d[4], d[5], s);
                      });
 }
 
@@ -1775,19 +1755,16 @@ int kite_nmpc_ident_normal_wind(kite_nmpc_ctx* ctx, const kite_ident_config* cfg
     if (rc) return rc;
     const size_t c = count, NPq = KITE_IDENT_NP;
     return run_items(ctx,
-                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {p21, c * NPq},
-                      {X, c * (T + 1) * 13}, {U, c * T * 3}, {W, W ? c * T * 3 : 0}},
-                     {{A, c * NPq * NPq}, {g, c * NPq}, {cost, c}, {nullptr, (c + 1) / 2},
-                      {nullptr, c * K.nchunks * kite::ID_SLAB}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         int32_t* dst = reinterpret_cast<int32_t*>(o[3]);
-                         hipError_t e = kite::launch_ident_accum(K, i[0], i[1], KITE_IDENT_NP, nullptr, i[2], i[3],
-                                                                 W ? i[4] : nullptr, o[4], s);
+                     {ks::in(reinterpret_cast<const double*>(params), (size_t)nparams * 52), ks::in(p21, c * NPq),
+                      ks::in(X, c * (T + 1) * 13), ks::in(U, c * T * 3), ks::in(W, W ? c * T * 3 : 0),
+                      ks::out(A, c * NPq * NPq), ks::out(g, c * NPq), ks::out(cost, c), ks::out(status, c),
+                      ks::scratch(c * K.nchunks * kite::ID_SLAB)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         hipError_t e = kite::launch_ident_accum(K, d[0], d[1], KITE_IDENT_NP, nullptr, d[2], d[3],
+                                                                 d[4], d[9], s);
                          if (e != hipSuccess) return e;
-                         e = kite::launch_ident_solve(K, 0, 1, i[0], i[1], o[4], nullptr, o[0], o[1], o[2], nullptr,
-                                                      nullptr, nullptr, dst, s);
-                         if (e != hipSuccess || !status) return e;
-                         return hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+                         return kite::launch_ident_solve(K, 0, 1, d[0], d[1], d[9], nullptr, d[5], d[6], d[7], nullptr,
+                                                         nullptr, nullptr, i32(d[8]), s);
                      });
 }
 
@@ -1829,23 +1806,14 @@ int kite_nmpc_identify_wind(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, in
     if (rc) return rc;
     const size_t c = count;
     const size_t ws = (size_t)kite_nmpc_ident_workspace_doubles(cfg, count, T);
-    // int32 outputs (evals, status) share one scratch block of c doubles
     return run_items(ctx,
-                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {X, c * (T + 1) * 13},
-                      {U, c * T * 3}, {W, W ? c * T * 3 : 0}},
-                     {{reinterpret_cast<double*>(params_out), c * 52}, {cost2, 2 * c}, {nullptr, c}, {nullptr, ws}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         int32_t* dev = reinterpret_cast<int32_t*>(o[2]);
-                         int32_t* dst = dev + c;
-                         if (ident_run_device(ctx, cfg, K, i[0], i[1], i[2], W ? i[3] : nullptr, o[0], o[1], dev, dst,
-                                              o[3]) != KITE_OK)
-                             return hipErrorLaunchFailure;
-                         if (evals) {
-                             hipError_t e = hipMemcpyAsync(evals, dev, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-                             if (e != hipSuccess) return e;
-                         }
-                         if (status) return hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-                         return hipSuccess;
+                     {ks::in(reinterpret_cast<const double*>(params), (size_t)nparams * 52),
+                      ks::in(X, c * (T + 1) * 13), ks::in(U, c * T * 3), ks::in(W, W ? c * T * 3 : 0),
+                      ks::out(reinterpret_cast<double*>(params_out), c * 52), ks::out(cost2, 2 * c),
+                      ks::out(evals, c), ks::out(status, c), ks::scratch(ws)},
+                     [&](std::vector<double*>& d, hipStream_t) {
+                         return ident_run_device(ctx, cfg, K, d[0], d[1], d[2], d[3], d[4], d[5], i32(d[6]),
+                                                 i32(d[7]), d[8]) == KITE_OK ? hipSuccess : hipErrorLaunchFailure;
                      });
 }
 
@@ -1918,12 +1886,12 @@ int kite_nmpc_ident_sens_joint(kite_nmpc_ctx* ctx, int32_t count, double h, int3
     if (rc) return rc;
     const size_t c = count;
     return run_items(ctx,
-                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {x13, c * 13}, {u3, c * 3},
-                      {w3, c * 3}},
-                     {{x13_out, c * 13}, {S, c * 13 * KITE_IDENT_NPW}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_ident_sens_jw(count, nparams, h / substeps, substeps, i[0], i[1], i[2],
-                                                           i[3], o[0], o[1], s);
+                     {ks::in(reinterpret_cast<const double*>(params), (size_t)nparams * 52), ks::in(x13, c * 13),
+                      ks::in(u3, c * 3), ks::in(w3, c * 3), ks::out(x13_out, c * 13),
+                      ks::out(S, c * 13 * KITE_IDENT_NPW)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_ident_sens_jw(count, nparams, h / substeps, substeps, d[0], d[1], d[2],
+                                                           d[3], d[4], d[5], s);
                      });
 }
 
@@ -1943,19 +1911,16 @@ int kite_nmpc_ident_normal_joint(kite_nmpc_ctx* ctx, const kite_ident_config* cf
     if (rc) return rc;
     const size_t c = count, NJ = KITE_IDENT_NPW;
     return run_items(ctx,
-                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {p21, c * KITE_IDENT_NP},
-                      {w3, c * 3}, {X, c * (T + 1) * 13}, {U, c * T * 3}, {W0, W0 ? c * T * 3 : 0}},
-                     {{A, c * NJ * NJ}, {g, c * NJ}, {cost, c}, {nullptr, (c + 1) / 2},
-                      {nullptr, c * K.nchunks * kite::IDJ_SLAB}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         int32_t* dst = reinterpret_cast<int32_t*>(o[3]);
-                         hipError_t e = kite::launch_ident_accum_jw(K, WK, i[0], i[1], i[2], KITE_IDENT_NP, 3, nullptr, i[3], i[4],
-                                                                    W0 ? i[5] : nullptr, o[4], s);
+                     {ks::in(reinterpret_cast<const double*>(params), (size_t)nparams * 52),
+                      ks::in(p21, c * KITE_IDENT_NP), ks::in(w3, c * 3), ks::in(X, c * (T + 1) * 13),
+                      ks::in(U, c * T * 3), ks::in(W0, W0 ? c * T * 3 : 0), ks::out(A, c * NJ * NJ), ks::out(g, c * NJ),
+                      ks::out(cost, c), ks::out(status, c), ks::scratch(c * K.nchunks * kite::IDJ_SLAB)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         hipError_t e = kite::launch_ident_accum_jw(K, WK, d[0], d[1], d[2], KITE_IDENT_NP, 3, nullptr,
+                                                                    d[3], d[4], d[5], d[10], s);
                          if (e != hipSuccess) return e;
-                         e = kite::launch_ident_solve24(K, WK, 0, 1, i[0], i[1], i[2], o[4], nullptr, o[0], o[1], o[2],
-                                                        nullptr, nullptr, nullptr, nullptr, dst, s);
-                         if (e != hipSuccess || !status) return e;
-                         return hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+                         return kite::launch_ident_solve24(K, WK, 0, 1, d[0], d[1], d[2], d[10], nullptr, d[6], d[7],
+                                                           d[8], nullptr, nullptr, nullptr, nullptr, i32(d[9]), s);
                      });
 }
 
@@ -1992,22 +1957,14 @@ int kite_nmpc_identify_joint(kite_nmpc_ctx* ctx, const kite_ident_config* cfg, c
     const size_t c = count;
     const size_t ws = (size_t)kite_nmpc_ident_joint_workspace_doubles(cfg, count, T);
     return run_items(ctx,
-                     {{reinterpret_cast<const double*>(params), (size_t)nparams * 52}, {X, c * (T + 1) * 13},
-                      {U, c * T * 3}, {W0, W0 ? c * T * 3 : 0}},
-                     {{reinterpret_cast<double*>(params_out), c * 52}, {wind_out, c * 3}, {cost2, 2 * c}, {nullptr, c},
-                      {nullptr, ws}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         int32_t* dev = reinterpret_cast<int32_t*>(o[3]);
-                         int32_t* dst = dev + c;
-                         if (ident_joint_run_device(ctx, cfg, K, WK, i[0], i[1], i[2], W0 ? i[3] : nullptr, o[0], o[1],
-                                                    o[2], dev, dst, o[4]) != KITE_OK)
-                             return hipErrorLaunchFailure;
-                         if (evals) {
-                             hipError_t e = hipMemcpyAsync(evals, dev, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-                             if (e != hipSuccess) return e;
-                         }
-                         if (status) return hipMemcpyAsync(status, dst, c * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-                         return hipSuccess;
+                     {ks::in(reinterpret_cast<const double*>(params), (size_t)nparams * 52),
+                      ks::in(X, c * (T + 1) * 13), ks::in(U, c * T * 3), ks::in(W0, W0 ? c * T * 3 : 0),
+                      ks::out(reinterpret_cast<double*>(params_out), c * 52), ks::out(wind_out, c * 3),
+                      ks::out(cost2, 2 * c), ks::out(evals, c), ks::out(status, c), ks::scratch(ws)},
+                     [&](std::vector<double*>& d, hipStream_t) {
+                         return ident_joint_run_device(ctx, cfg, K, WK, d[0], d[1], d[2], d[3], d[4], d[5], d[6],
+                                                       i32(d[7]), i32(d[8]), d[9]) == KITE_OK
+                                    ? hipSuccess : hipErrorLaunchFailure;
                      });
 }
 
@@ -2017,12 +1974,12 @@ int kite_nmpc_rk4_sens(kite_nmpc_ctx* ctx, int32_t count, const double* x15, con
     const size_t c = count;
     const double h = tf / M;
     // scratch outputs (no host copy): X2 [c][2][15], AB [c][13][16], DEF [c][13]
-    return run_items(ctx, {{x15, c * 15}, {u4, c * 4}},
-                     {{xnext, c * 15}, {A, c * 225}, {Bm, c * 60}, {nullptr, c * 30}, {nullptr, c * 208},
-                      {nullptr, c * 13}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_rk4_sens_items(ctx->mc, ctx->rc.sens_fp32, count, M, h, i[0], i[1],
-                                                            o[0], o[1], o[2], o[3], o[4], o[5], s);
+    return run_items(ctx,
+                     {ks::in(x15, c * 15), ks::in(u4, c * 4), ks::out(xnext, c * 15), ks::out(A, c * 225),
+                      ks::out(Bm, c * 60), ks::scratch(c * 30), ks::scratch(c * 208), ks::scratch(c * 13)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_rk4_sens_items(ctx->mc, ctx->rc.sens_fp32, count, M, h, d[0], d[1],
+                                                            d[2], d[3], d[4], d[5], d[6], d[7], s);
                      });
 }
 
@@ -2032,9 +1989,9 @@ int kite_nmpc_closest_point(kite_nmpc_ctx* ctx, int32_t count, const double* pos
     const size_t c = count;
     std::vector<double> g;
     if (!guess) g.assign(c, 0.0);
-    return run_items(ctx, {{pos, c * 3}, {guess ? guess : g.data(), c}}, {{theta_out, c}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_closest_point(ctx->rc, count, i[0], i[1], o[0], s);
+    return run_items(ctx, {ks::in(pos, c * 3), ks::in(guess ? guess : g.data(), c), ks::out(theta_out, c)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_closest_point(ctx->rc, count, d[0], d[1], d[2], s);
                      });
 }
 
@@ -2076,6 +2033,12 @@ kite::ScoreConst make_score_const(const kite_nmpc_ctx* ctx) {
     std::memcpy(S.pF, rc.pF, sizeof(S.pF));
     return S;
 }
+
+// the checks of kite_nmpc_score_step and its _device twin (pointers of either side)
+int score_check(const kite_nmpc_ctx* ctx, int32_t count, const double* x13, const double* u4, const double* acc,
+                const double* mem) {
+    return (!ctx || count < 1 || !x13 || !u4 || !acc || !mem) ? KITE_EINVAL : KITE_OK;
+}
 }  // namespace
 }  // extern "C++"
 
@@ -2093,16 +2056,17 @@ int kite_nmpc_closest_point_global(kite_nmpc_ctx* ctx, int32_t count, const doub
     if (!ctx || count < 1 || !pos3 || !theta_out || !dist_out) return KITE_EINVAL;
     const size_t c = count;
     const kite::ScoreConst S = make_score_const(ctx);
-    return run_items(ctx, {{pos3, c * 3}}, {{theta_out, c}, {dist_out, c}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_closest_point_global(S, count, i[0], o[0], o[1], s);
+    return run_items(ctx, {ks::in(pos3, c * 3), ks::out(theta_out, c), ks::out(dist_out, c)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_closest_point_global(S, count, d[0], d[1], d[2], s);
                      });
 }
 
 int kite_nmpc_score_step_device(kite_nmpc_ctx* ctx, int32_t count, const double* d_x13, const double* d_u4,
                                 const int32_t* d_status, const int32_t* d_plant_status, int32_t first, double* d_acc,
                                 double* d_mem) {
-    if (!ctx || count < 1 || !d_x13 || !d_u4 || !d_acc || !d_mem) return KITE_EINVAL;
+    const int rc = score_check(ctx, count, d_x13, d_u4, d_acc, d_mem);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(kite::launch_score(make_score_const(ctx), count, d_x13, d_u4, d_status, d_plant_status, first != 0,
                                d_acc, d_mem, ctx->stream));
@@ -2112,28 +2076,16 @@ int kite_nmpc_score_step_device(kite_nmpc_ctx* ctx, int32_t count, const double*
 int kite_nmpc_score_step(kite_nmpc_ctx* ctx, int32_t count, const double* x13, const double* u4,
                          const int32_t* status, const int32_t* plant_status, int32_t first, double* acc,
                          double* mem) {
-    if (!ctx || count < 1 || !x13 || !u4 || !acc || !mem) return KITE_EINVAL;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t c = count;
-    const size_t nx = c * 13, nu = c * 4, na = c * KITE_SCORE_NACC, nm = c * KITE_SCORE_NMEM, ns = (c + 1) / 2;
-    int rc = ensure_scratch(ctx, (nx + nu + na + nm + 2 * ns) * sizeof(double));
+    const int rc = score_check(ctx, count, x13, u4, acc, mem);
     if (rc) return rc;
-    double *dx = ctx->scratch, *du = dx + nx, *da = du + nu, *dm = da + na;
-    int32_t* dst = reinterpret_cast<int32_t*>(dm + nm);
-    int32_t* dps = reinterpret_cast<int32_t*>(dm + nm + ns);
-    hipStream_t s = ctx->stream;
-    HIP_TRY(hipMemcpyAsync(dx, x13, nx * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(du, u4, nu * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(da, acc, na * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dm, mem, nm * sizeof(double), hipMemcpyHostToDevice, s));
-    if (status) HIP_TRY(hipMemcpyAsync(dst, status, c * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (plant_status) HIP_TRY(hipMemcpyAsync(dps, plant_status, c * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(kite::launch_score(make_score_const(ctx), count, dx, du, status ? dst : nullptr,
-                               plant_status ? dps : nullptr, first != 0, da, dm, s));
-    HIP_TRY(hipMemcpyAsync(acc, da, na * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(mem, dm, nm * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return KITE_OK;
+    const size_t c = count;
+    return run_items(ctx,
+                     {ks::in(x13, c * 13), ks::in(u4, c * 4), ks::inout(acc, c * KITE_SCORE_NACC),
+                      ks::inout(mem, c * KITE_SCORE_NMEM), ks::in(status, c), ks::in(plant_status, c)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_score(make_score_const(ctx), count, d[0], d[1], i32(d[4]), i32(d[5]),
+                                                   first != 0, d[2], d[3], s);
+                     });
 }
 
 int kite_nmpc_score_summary_device(kite_nmpc_ctx* ctx, int32_t count, const double* d_acc, double* d_out16) {
@@ -2146,9 +2098,9 @@ int kite_nmpc_score_summary_device(kite_nmpc_ctx* ctx, int32_t count, const doub
 int kite_nmpc_score_summary(kite_nmpc_ctx* ctx, int32_t count, const double* acc, double* out16) {
     if (!ctx || count < 1 || !acc || !out16) return KITE_EINVAL;
     const size_t c = count;
-    return run_items(ctx, {{acc, c * KITE_SCORE_NACC}}, {{out16, KITE_SCORE_NSUM}},
-                     [&](std::vector<double*>& i, std::vector<double*>& o, hipStream_t s) {
-                         return kite::launch_score_summary(count, i[0], o[0], s);
+    return run_items(ctx, {ks::in(acc, c * KITE_SCORE_NACC), ks::out(out16, KITE_SCORE_NSUM)},
+                     [&](std::vector<double*>& d, hipStream_t s) {
+                         return kite::launch_score_summary(count, d[0], d[1], s);
                      });
 }
 

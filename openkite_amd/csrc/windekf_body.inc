@@ -74,58 +74,16 @@
     if (z) {                                 // uniform over the grid
         for (int i = 0; i < WEKF_N; ++i) sn[i * WEKF_LD + j] = pcol[i];
         __syncthreads();
-        // S = P+[6:13, 6:13] + V, Cholesky in registers (lower), every lane its own copy
+        // the pose update: ekf_update.hpp
         double L[7][7];
-        for (int a = 0; a < 7; ++a)
-            for (int c = 0; c <= a; ++c) L[a][c] = kite ? sn[(6 + a) * WEKF_LD + 6 + c] + V[a * 7 + c] : (a == c);
-        bool pd = true;
-        for (int c = 0; c < 7; ++c) {
-            double d = L[c][c];
-            for (int k = 0; k < c; ++k) d -= L[c][k] * L[c][k];
-            pd = pd && (d > 0.0) && isfinite(d);
-            d = sqrt(d);
-            L[c][c] = d;
-            for (int a = c + 1; a < 7; ++a) {
-                double t = L[a][c];
-                for (int k = 0; k < c; ++k) t -= L[a][k] * L[c][k];
-                L[a][c] = t / d;
-            }
-        }
-        auto solve = [&](double r[7]) {          // r <- S^-1 r
-            for (int a = 0; a < 7; ++a) {
-                double t = r[a];
-                for (int k = 0; k < a; ++k) t -= L[a][k] * r[k];
-                r[a] = t / L[a][a];
-            }
-            for (int a = 6; a >= 0; --a) {
-                double t = r[a];
-                for (int k = a + 1; k < 7; ++k) t -= L[k][a] * r[k];
-                r[a] = t / L[a][a];
-            }
-        };
-        // P[:, j] = P+[:, j] - P+[:, 6:13] S^-1 P+[6:13, j]
-        double pu[WEKF_N], xu[WEKF_N];
-        {
-            double c7[7];
-            for (int a = 0; a < 7; ++a) c7[a] = pcol[6 + a];
-            solve(c7);
-            for (int i = 0; i < WEKF_N; ++i) {
-                double t = pcol[i];
-                for (int a = 0; a < 7; ++a) t = fma(-sn[i * WEKF_LD + 6 + a], c7[a], t);
-                pu[i] = t;
-            }
-        }
-        // x = x+ + P+[:, 6:13] S^-1 (z - x+[6:13])
-        {
-            double y[7];
-            for (int a = 0; a < 7; ++a) y[a] = (kite ? z[(size_t)b * 7 + a] : 0.0) - xv[6 + a];
-            solve(y);
-            for (int i = 0; i < WEKF_N; ++i) {
-                double t = xv[i];
-                for (int a = 0; a < 7; ++a) t = fma(sn[i * WEKF_LD + 6 + a], y[a], t);
-                xu[i] = t;
-            }
-        }
+        const bool pd = ekf_chol7<WEKF_LD>(sn, V, kite, L);
+        double pu[WEKF_N], xu[WEKF_N], y[7];
+        ekf_cov_update<WEKF_N, WEKF_LD>(sn, L, pcol, pu);
+        for (int a = 0; a < 7; ++a) y[a] = (kite ? z[(size_t)b * 7 + a] : 0.0) - xv[6 + a];
+        ekf_state_update<WEKF_N, WEKF_LD>(sn, L, xv, y, xu);
+        // The containment tail, ekf_commit's statements (the reason for the
+        // symmetrisation is written there).  This filter keeps its own copy:
+        // through ekf_commit k_ekf_wind_pk is scheduled 1.2 % slower.
         bool ok = true;
         for (int i = 0; i < WEKF_N; ++i) ok = ok && isfinite(pu[i]) && isfinite(xu[i]);
         const bool bad = kite_any(!ok, kk);
@@ -135,12 +93,7 @@
         if (updated) {
             for (int i = 0; i < WEKF_N; ++i) { pcol[i] = pu[i]; xv[i] = xu[i]; }
         }
-        // P <- (P + P') / 2 of an updated kite.  S is factored from its lower
-        // triangle alone, so the update does not damp an antisymmetric part of
-        // P: rounding seeds one and every further update multiplies it (by 1.4
-        // to 1.6 per period in the open-loop run of the tests: 1e-15 becomes
-        // 1e-10 within 40 periods and O(1) within 100).  Both halves of a pair
-        // add the same two numbers, so P leaves exactly symmetric.
+        // P <- (P + P') / 2 of an updated kite
         __syncthreads();                     // every lane is done with P+ in sn
         for (int i = 0; i < WEKF_N; ++i) sn[i * WEKF_LD + j] = pcol[i];
         __syncthreads();

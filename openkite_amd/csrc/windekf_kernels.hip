@@ -10,10 +10,13 @@
 //     A   = I_16 + J h,  J = [df/dx | df/dW ; 0_{3x16}] under the estimated wind
 //     x13 <- one RK4 step of kite_rhs<double, true> under that wind, W unchanged
 //     P   <- A P A' + Wcov
-//   then, with a measurement z, one update as k_ekf does it:
+//   then, with a measurement z, one update (ekf_update.hpp, shared with k_ekf
+//   and k_ekf_kin):
 //     S = P[6:13, 6:13] + V (7 x 7 Cholesky in registers),
 //     x <- x + P[:, 6:13] S^-1 (z - x[6:13]),  P <- P - P[:, 6:13] S^-1 P[6:13, :]
-//   and, beyond k_ekf, P <- (P + P') / 2 after the update (see there)
+//   and, beyond k_ekf, the containment tail: the flags and P <- (P + P') / 2
+//   after the update (this filter's own copy of ekf_commit's statements;
+//   the reason for the symmetrisation is written at ekf_commit)
 //
 // Lane layout: k_ekf's -- lane j of a kite's 16 owns column j of the 16 x 16
 // matrices, 4 kites per wavefront, 64-thread blocks -- with every lane busy:
@@ -33,6 +36,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "ekf_update.hpp"
 #include "kite_model.hpp"
 #include "kite_nmpc/kite_nmpc.h"
 #include "rti_kernels.hpp"
@@ -54,12 +58,6 @@ __device__ __forceinline__ void wind_jac_col(const ModelConst& P, const double* 
     for (int i = 0; i < 3; ++i) ww[i] = mk(wv[i], NK + i == j ? 1.0 : 0.0);
     kite_rhs<Dual, true, Dual>(P, xx, uu, ff, ww);
     for (int i = 0; i < NK; ++i) col[i] = ff[i].t;
-}
-
-// true when any of the calling kite's 16 lanes passes bad (kk: kite of the wave)
-__device__ __forceinline__ bool kite_any(bool bad, int kk) {
-    const unsigned long long m = __ballot(bad);
-    return ((m >> (kk * 16)) & 0xFFFFull) != 0;
 }
 
 __global__ __launch_bounds__(WEKF_T) void k_ekf_wind(ModelConst P, int count, double dt, int substeps,

@@ -240,6 +240,24 @@ def test_init_flags_what_it_cannot_initialise(ctx):
     np.testing.assert_array_equal(np.delete(x1, 1, 0), np.delete(good, 1, 0))
 
 
+@pytest.mark.parametrize("framed", [False, True])
+def test_init_host_equals_device(ctx, framed):
+    """kin_ekf_init and kin_ekf_init_device at count 5, one pose non-finite: the same bits."""
+    B = 5
+    prev, new = _poses(B)
+    new[3, 1] = np.nan
+    fr = ok.pose_frame_default() if framed else None
+    keep = np.arange(B * 13, dtype=np.float64).reshape(B, 13)
+    xh, sh = ctx.kin_ekf_init(prev, new, DT, fr, keep)
+    dp, dn, dx = (torch.from_numpy(a.copy()).cuda() for a in (prev, new, keep))
+    st = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+    ctx.kin_ekf_init_device(B, DT, dp.data_ptr(), dn.data_ptr(), dx.data_ptr(), st.data_ptr(), frame=fr)
+    ctx.synchronize()
+    np.testing.assert_array_equal(sh, [0, 0, 0, ok.EKF_INIT_BAD, 0])
+    np.testing.assert_array_equal(dx.cpu().numpy(), xh)
+    np.testing.assert_array_equal(st.cpu().numpy(), sh)
+
+
 def test_bad_arguments(ctx):
     x, P, z, W, V = inputs(2)
 
