@@ -70,7 +70,11 @@ extern "C" {
                                       KITE_IDENT_WIND_AT_BOUND) and the actuation
                                       delay (kite_nmpc_plant_step_delayed[_device],
                                       KITE_DELAY_*, KITE_PLANT_CMD_DROPPED,
-                                      KITE_PLANT_BAD_TAU)                         */
+                                      KITE_PLANT_BAD_TAU) and the line's transport
+                                      rule and the in-flight schedule
+                                      (KITE_DELAY_RULE*, kite_nmpc_set_inflight[_device],
+                                      _get_inflight, KITE_INFLIGHT_N,
+                                      KITE_ST_BAD_INFLIGHT)                       */
 #define KITE_PATH_MAX_HARMONICS 8 /* Fourier path: harmonics per axis              */
 
 /* ---- error codes ------------------------------------------------------ */
@@ -98,6 +102,9 @@ extern "C" {
 #define KITE_ST_RESTART       64   /* the warm start held non-finite values: this kite
                                       was restarted cold, theta from the closest point
                                       and thetadot = 0 (nmpf_node.cpp:225-236)        */
+#define KITE_ST_BAD_INFLIGHT 128   /* the kite's in-flight schedule row is invalid (n = -1,
+                                      kite_nmpc_set_inflight): the delay compensation
+                                      predicted under the previous u(t0) instead        */
 
 /* ---- model parameters: kite_utils::LoadProperties (kite.cpp:7-76) ------
  * Field order == KiteProperties (kite.h:9-93) flattened.  52 doubles.     */
@@ -159,7 +166,9 @@ typedef struct kite_nmpc_config {
                              and theta, thetadot are taken from the previous trajectory
                              at node round(delay/dt).  0 = off: KiteNMPF semantics, the
                              caller passes the predicted state (default).  The node
-                             uses 0.1 (nmpf_node.cpp:74).                              */
+                             uses 0.1 (nmpf_node.cpp:74).  With an in-flight schedule
+                             (kite_nmpc_set_inflight) the prediction runs under the
+                             commands still in the line, piecewise constant.           */
     int32_t sens_fp32;    /* 1: RK4 + forward sensitivities in fp32 (mixed precision,
                              BASELINE config 4); condensing, QP, expansion stay fp64 */
     int32_t reserved;
@@ -347,6 +356,15 @@ int kite_nmpc_plant_step_device(kite_nmpc_ctx* ctx, double* d_x13, const double*
  *           channel never reorders.  tau[b] negative or non-finite: the
  *           command is dropped, KITE_PLANT_BAD_TAU.  A send to a full line
  *           drops the OLDEST pending command, KITE_PLANT_CMD_DROPPED.
+ *           That is KITE_DELAY_RULE_SEQUENTIAL: every accepted command is
+ *           charged its latency after the one before it, so a latency above
+ *           the control period makes the line fall behind.  A line whose
+ *           KITE_DELAY_RULE slot holds exactly 1.0 (KITE_DELAY_RULE_TRANSPORT)
+ *           takes t_arr = max(t_send + tau[b], t_arr_prev) instead (t_arr_prev
+ *           only once a command has been accepted): a pure transport delay,
+ *           clamped so that the channel still never reorders.  Everything else
+ *           of the send is the same under both rules; the rule is per line,
+ *           the caller writes the slot and the calls carry it through.
  *   fly     before plant step j (j = 0 .. steps-1) every pending command with
  *           t_arr <= t_j leaves the FIFO in order and the last of them becomes
  *           the control in force; t_j = t0 + (double)(j * substeps) * (h /
@@ -363,7 +381,10 @@ int kite_nmpc_plant_step_device(kite_nmpc_ctx* ctx, double* d_x13, const double*
 #define KITE_DELAY_COUNT        0    /* pending commands, 0 .. KITE_DELAY_DEPTH           */
 #define KITE_DELAY_T_PREV       1    /* arrival time of the last accepted command         */
 #define KITE_DELAY_HAS_PREV     2    /* 1 once a command has been accepted, else 0        */
-                                     /* 3: reserved, zero                                 */
+#define KITE_DELAY_RULE         3    /* the arrival rule: exactly 1.0 is KITE_DELAY_RULE_TRANSPORT,
+                                        any other value (NaN included) _SEQUENTIAL       */
+#define KITE_DELAY_RULE_SEQUENTIAL 0 /* t_arr = max(t_send, t_arr_prev) + tau             */
+#define KITE_DELAY_RULE_TRANSPORT  1 /* t_arr = max(t_send + tau, t_arr_prev)             */
 #define KITE_DELAY_U_FORCE      4    /* 4..7: the control in force (T, dE, dR, 4th)       */
 #define KITE_DELAY_T_ARR        8    /* 8..11: arrival times, slot 0 the oldest           */
 #define KITE_DELAY_U            12   /* 12..27: the pending commands, 4 doubles per slot  */
@@ -384,6 +405,50 @@ int kite_nmpc_plant_step_delayed(kite_nmpc_ctx* ctx, double* x13, const double* 
 int kite_nmpc_plant_step_delayed_device(kite_nmpc_ctx* ctx, double* d_x13, const double* d_u4_cmd,
                                         const double* d_tau, double* d_line, double* d_u4_applied, double t0,
                                         double h, int32_t steps, int32_t substeps, int32_t* d_status);
+
+/* ---- the in-flight schedule: the line as the controller sees it -----------
+ * The delay compensation (config.delay) predicts the measured state over the
+ * delay under ONE control, the previous u(t0).  With a latency above one
+ * control period the line holds several different commands.  The in-flight
+ * schedule is a snapshot of every kite's line at time t0, kept by the context:
+ * a row of KITE_INFLIGHT_N doubles per kite,
+ *   [0]      n, the number of switches: the pending count as the send reads it
+ *            (0 .. KITE_DELAY_DEPTH, NaN read as 0), or -1: the row is invalid
+ *   [1..4]   s_i, seconds after t0 at which pending command i takes over:
+ *            max(t_arr_i - t0, 0), then a running maximum over i (the FIFO pops
+ *            in order)
+ *   [5..7]   the control in force (T, dE, dR)
+ *   [8..19]  the pending commands (T, dE, dR), oldest first
+ *   rest     zero; unused entries are zero
+ * A non-finite control in force, or a non-finite arrival time or (T, dE, dR) of
+ * one of the n pending commands, makes the row invalid: n = -1, the rest zero.
+ * The 4th control of a command is not part of the kite model and is ignored.
+ *
+ * With a schedule set, a warm step with config.delay = D > 0 predicts every
+ * kite with a valid row over [0, D] under the piecewise-constant control: the
+ * control in force until s_1, command i from s_i until s_{i+1}, the last to D.
+ * Switches with s_i >= D are ignored and zero-length pieces are skipped (a
+ * command superseded at the same instant never flies).  A piece of length L
+ * takes n RK4 substeps of L / n, n the smallest integer in 1 .. delay_steps
+ * with (double)n * (D / delay_steps) >= L (delay_steps if there is none): a
+ * window without a switch is the prediction without a schedule, bit for bit.
+ * A kite with an invalid row is predicted under the previous u(t0) and flagged
+ * KITE_ST_BAD_INFLIGHT.  Cold steps have no compensation and ignore it.
+ *
+ * The schedule stays in force, as stored, until it is replaced or switched
+ * off with NULL; kite_nmpc_reset keeps it.  The caller refreshes it every
+ * period, right before the step.  config.delay == 0 with a schedule, or
+ * _get_inflight without one: KITE_ESTATE, nothing changes.  Non-finite t0:
+ * KITE_EINVAL.  The switch times are the arrival instants; the plant applies a
+ * command at its next tick (see above), a gap of less than one plant step.  */
+#define KITE_INFLIGHT_N 24  /* doubles per kite */
+/* d_line: B x KITE_DELAY_NLINE in device memory (read in stream order, not
+ * changed), asynchronous on the context stream.                             */
+int kite_nmpc_set_inflight_device(kite_nmpc_ctx* ctx, const double* d_line, double t0);
+/* Same, host pointer.                                                       */
+int kite_nmpc_set_inflight(kite_nmpc_ctx* ctx, const double* line, double t0);
+/* The schedule rows in force, B x KITE_INFLIGHT_N (host pointer; tests).    */
+int kite_nmpc_get_inflight(kite_nmpc_ctx* ctx, double* sched);
 
 /* ---- introspection (tests, profiling) ---------------------------------- */
 /* ---- reference formulation: Chebyshev collocation (chebyshev.hpp) -------

@@ -6,7 +6,8 @@ include/kite_nmpc/kite_nmpc.h); this package is its Python host side.
 from .nmpc import (BatchNMPC, CollocConfig, KiteEKF, KiteNMPF, KiteNmpcError, KiteParams, NmpcConfig, MpcDiagnostic,  # noqa: F401
                    colloc_default_config, default_config, ekf_default_covariances, load_properties, lib, LIB_PATH, DIAG_FIELDS,
                    path_eval, perturb_params, resolve_qp_kernel, PERTURB_FIELDS, PLANT_NAN,
-                   PLANT_CMD_DROPPED, PLANT_BAD_TAU, DELAY_DEPTH, DELAY_NLINE,
+                   PLANT_CMD_DROPPED, PLANT_BAD_TAU, DELAY_DEPTH, DELAY_NLINE, DELAY_RULE, DELAY_RULE_SEQUENTIAL,
+                   DELAY_RULE_TRANSPORT, ST_BAD_INFLIGHT, INFLIGHT_N,
                    wind_ekf_default_covariances, EKF_NAN, EKF_S_NOT_PD, WIND_MAX_DEFAULT,
                    EST_MODEL_CREATION, EST_MODEL_CONTROLLER, QP_SPLIT_AUTO, QP_SPLIT_NEVER, EKF_INIT_BAD, PoseFrame, pose_frame_default,
                    IdentConfig, IdentResult, ident_default_config, ident_param_index, ident_workspace_doubles,

@@ -77,6 +77,8 @@ struct kite_nmpc_ctx {
     double *Htl = nullptr, *Hab = nullptr, *Hbb = nullptr;
     double* wind = nullptr;        // per-kite world-frame wind B x 3 (kite_nmpc_set_wind)
     bool has_wind = false;         // a nonzero wind is set: the WIND kernels run
+    double* inflight = nullptr;    // in-flight schedule B x KITE_INFLIGHT_N (kite_nmpc_set_inflight), allocated once
+    bool has_inflight = false;     // a schedule is in force: the prologue predicts under it
     // the model of the step's predictions (kite_nmpc_set_params[_device]); mc and
     // params stay the creation model, which every item-wise entry point keeps
     int model_mode = 0;            // 0: mc; 1: model_mc1 for all (kernel argument); 2: the table
@@ -311,7 +313,8 @@ void free_ctx(kite_nmpc_ctx* ctx) {
     double** bufs[] = {&ctx->X, &ctx->U, &ctx->x0, &ctx->AB, &ctx->DEF, &ctx->Hs, &ctx->hs,
                        &ctx->Cr, &ctx->cl, &ctx->cu, &ctx->hmax, &ctx->u0, &ctx->diag, &ctx->kkt,
                        &ctx->scratch, &ctx->Htl, &ctx->Hab, &ctx->Hbb, &ctx->wstep, &ctx->wind,
-                       &ctx->plant_mc, &ctx->plant_wind, &ctx->model_tab, &ctx->model_rows, &ctx->qp_ckpt};
+                       &ctx->plant_mc, &ctx->plant_wind, &ctx->model_tab, &ctx->model_rows, &ctx->qp_ckpt,
+                       &ctx->inflight};
     for (double** p : bufs) if (*p) { (void)hipFree(*p); *p = nullptr; }
     if (ctx->dconst) { (void)hipFree(ctx->dconst); ctx->dconst = nullptr; }
     if (ctx->status) { (void)hipFree(ctx->status); ctx->status = nullptr; }
@@ -387,7 +390,7 @@ int run_step(kite_nmpc_ctx* ctx, const double* x0) {
     const ModelConst& mc = ctx->model_mode == 1 ? ctx->model_mc1 : ctx->mc;
     const double* mct = ctx->model_mode == 2 ? ctx->model_tab : nullptr;
     HIP_TRY(kite::launch_prologue(mc, ctx->rc, B, ctx->warm ? 1 : 0, x0, ctx->X, ctx->U, ctx->status,
-                                  wind, ctx->order + 2 * B + 1, mct, s));
+                                  wind, ctx->order + 2 * B + 1, mct, ctx->has_inflight ? ctx->inflight : nullptr, s));
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
     HIP_TRY(kite::launch_rk4_sens(mc, ctx->rc, B, ctx->X, ctx->U, ctx->AB, ctx->DEF, wind, mct, s));
     if (ev) HIP_TRY(hipEventRecord(ev[2], s));
@@ -1107,6 +1110,70 @@ int kite_nmpc_plant_step_delayed(kite_nmpc_ctx* ctx, double* x13, const double* 
                          return plant_delay_launch(ctx, d[0], d[1], d[2], d[3], d[4], t0, h, steps, substeps,
                                                    i32(d[5]), s);
                      });
+}
+
+// ---- the in-flight schedule: the line as the delay compensation sees it -------
+extern "C++" {
+namespace {
+// the checks both setters share; KITE_OK with *off set: the schedule was switched off
+int inflight_begin(kite_nmpc_ctx* ctx, const void* line, double t0, bool* off) {
+    *off = false;
+    if (!ctx) return KITE_EINVAL;
+    if (!line) {
+        if (ctx->has_inflight) {
+            ctx->has_inflight = false;
+            ++ctx->graph_gen;                        // the prologue takes no schedule again
+        }
+        *off = true;
+        return KITE_OK;
+    }
+    if (!std::isfinite(t0)) return KITE_EINVAL;
+    if (!(ctx->cfg.delay > 0.0)) return KITE_ESTATE;     // nothing predicts: there is no window
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->inflight) HIP_TRY(hipMalloc(&ctx->inflight, (size_t)ctx->B * KITE_INFLIGHT_N * sizeof(double)));
+    return KITE_OK;
+}
+// the captured step reads ctx->inflight when it runs: a refresh of the rows
+// needs no new graph, only switching the schedule on or off does
+void inflight_on(kite_nmpc_ctx* ctx) {
+    if (!ctx->has_inflight) {
+        ctx->has_inflight = true;
+        ++ctx->graph_gen;
+    }
+}
+}  // namespace
+}  // extern "C++"
+
+int kite_nmpc_set_inflight_device(kite_nmpc_ctx* ctx, const double* d_line, double t0) {
+    bool off;
+    const int rc = inflight_begin(ctx, d_line, t0, &off);
+    if (rc || off) return rc;
+    HIP_TRY(kite::launch_inflight(ctx->B, d_line, t0, ctx->inflight, ctx->stream));
+    inflight_on(ctx);
+    return KITE_OK;
+}
+
+int kite_nmpc_set_inflight(kite_nmpc_ctx* ctx, const double* line, double t0) {
+    bool off;
+    int rc = inflight_begin(ctx, line, t0, &off);
+    if (rc || off) return rc;
+    rc = run_items(ctx, {ks::in(line, (size_t)ctx->B * KITE_DELAY_NLINE)},
+                   [&](std::vector<double*>& d, hipStream_t s) {
+                       return kite::launch_inflight(ctx->B, d[0], t0, ctx->inflight, s);
+                   });
+    if (rc) return rc;
+    inflight_on(ctx);
+    return KITE_OK;
+}
+
+int kite_nmpc_get_inflight(kite_nmpc_ctx* ctx, double* sched) {
+    if (!ctx || !sched) return KITE_EINVAL;
+    if (!ctx->has_inflight) return KITE_ESTATE;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(sched, ctx->inflight, (size_t)ctx->B * KITE_INFLIGHT_N * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return KITE_OK;
 }
 
 // ---- Chebyshev collocation evaluator (chebyshev.hpp) ------------------------

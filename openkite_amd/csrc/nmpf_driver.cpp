@@ -9,7 +9,8 @@
 //               [--ctrl-every K] [--sim-dt h] [--delay d] [--trace T] [--seed s]
 //               [--out file.jsonl] [--device i]
 //               [--plant-params file.csv] [--plant-wind file.csv]
-//               [--plant-delay SECONDS [--plant-delay-dev SECONDS] [--plant-delay-seed S]]
+//               [--plant-delay SECONDS [--plant-delay-dev SECONDS] [--plant-delay-seed S]
+//                [--plant-delay-rule sequential|transport] [--delay-comp last|queue]]
 //
 // --plant-params (B rows of the 52 kite_params values) and --plant-wind (B rows
 // of [W0 (3) | A (3) | f_hz | phase]) give every kite a plant of its own, which
@@ -27,7 +28,13 @@
 // step, with or without --plant-params / --plant-wind, and the summary line
 // gains "cmd_dropped", the kites whose full line dropped its oldest command in
 // the period before this step's measurement.  --delay is the controller's
-// assumption, --plant-delay is the plant's truth.
+// assumption, --plant-delay is the plant's truth.  --plant-delay-rule chooses
+// the line's arrival rule (kite_nmpc.h, KITE_DELAY_RULE_*): sequential (the
+// default) charges every command its latency after the one before it,
+// transport is a pure transport delay that never reorders.  --delay-comp queue
+// (it needs --plant-delay) hands the lines to the controller before every step
+// (kite_nmpc_set_inflight): the delay compensation then predicts under the
+// commands still in flight, not under the last u(t0) alone (last, the default).
 //
 // Timeline (per control step, all kites in lockstep):
 //   measure x (13 plant states) -> kite_nmpc_step (prologue predicts over
@@ -55,6 +62,8 @@ struct Args {
     double sim_dt = 0.02, delay = 0.1;
     double plant_delay = -1.0, plant_delay_dev = 0.0;      // < 0: no command line
     unsigned long long seed = 20261015ull, plant_delay_seed = 0ull;
+    int plant_delay_rule = KITE_DELAY_RULE_SEQUENTIAL;
+    bool comp_queue = false;
 };
 
 [[noreturn]] void usage(const char* argv0) {
@@ -62,7 +71,8 @@ struct Args {
                  "usage: %s [--params yaml] [--batch B] [--steps S] [--x0 file.csv] [--ctrl-every K]\n"
                  "          [--sim-dt h] [--delay d] [--trace T] [--seed s] [--out file.jsonl] [--device i]\n"
                  "          [--plant-params file.csv] [--plant-wind file.csv]\n"
-                 "          [--plant-delay seconds [--plant-delay-dev seconds] [--plant-delay-seed S]]\n",
+                 "          [--plant-delay seconds [--plant-delay-dev seconds] [--plant-delay-seed S]\n"
+                 "           [--plant-delay-rule sequential|transport] [--delay-comp last|queue]]\n",
                  argv0);
     std::exit(2);
 }
@@ -91,8 +101,20 @@ Args parse(int argc, char** argv) {
         else if (k == "--plant-delay") { a.plant_delay = std::atof(val()); if (!(a.plant_delay >= 0)) usage(argv[0]); }
         else if (k == "--plant-delay-dev") a.plant_delay_dev = std::atof(val());
         else if (k == "--plant-delay-seed") a.plant_delay_seed = std::strtoull(val(), nullptr, 10);
+        else if (k == "--plant-delay-rule") {
+            const std::string v = val();
+            if (v == "transport") a.plant_delay_rule = KITE_DELAY_RULE_TRANSPORT;
+            else if (v == "sequential") a.plant_delay_rule = KITE_DELAY_RULE_SEQUENTIAL;
+            else usage(argv[0]);
+        } else if (k == "--delay-comp") {
+            const std::string v = val();
+            if (v == "queue") a.comp_queue = true;
+            else if (v == "last") a.comp_queue = false;
+            else usage(argv[0]);
+        }
         else usage(argv[0]);
     }
+    if (a.comp_queue && !(a.plant_delay >= 0.0)) usage(argv[0]);      // there is no line to look at
     if (!std::isfinite(a.plant_delay) || !(a.plant_delay_dev >= 0) || !std::isfinite(a.plant_delay_dev)) usage(argv[0]);
     if (a.batch < 1 || a.steps < 0 || a.ctrl_every < 1 || !(a.sim_dt > 0) || a.trace < 0) usage(argv[0]);
     return a;
@@ -188,6 +210,7 @@ int main(int argc, char** argv) {
                                                     a.plant_delay + a.plant_delay_dev);
     if (delayed) {
         line.assign((size_t)B * KITE_DELAY_NLINE, 0.0);
+        for (int b = 0; b < B; ++b) line[(size_t)b * KITE_DELAY_NLINE + KITE_DELAY_RULE] = (double)a.plant_delay_rule;
         tau.assign((size_t)B, a.plant_delay);
         u_applied.assign((size_t)B * 4, 0.0);
     }
@@ -223,6 +246,11 @@ int main(int argc, char** argv) {
             std::memcpy(xb, &plant[(size_t)b * 13], 13 * sizeof(double));
             xb[13] = s == 0 ? theta[b] : traj[(size_t)b * (N + 1) * 15 + 15 + 13];
             xb[14] = s == 0 ? 0.0 : traj[(size_t)b * (N + 1) * 15 + 15 + 14];
+        }
+        if (a.comp_queue) {
+            // the lines as they stand at the measurement: what is in flight
+            rc = kite_nmpc_set_inflight(ctx, line.data(), t);
+            if (rc) return fail("in-flight schedule", rc);
         }
         const auto c0 = std::chrono::steady_clock::now();
         rc = kite_nmpc_step(ctx, x0.data(), u0.data(), traj.data(), nullptr, diag.data(), status.data());

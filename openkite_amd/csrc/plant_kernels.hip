@@ -21,6 +21,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "delay_line.hpp"
 #include "kite_model.hpp"
 #include "kite_nmpc/kite_nmpc.h"
 #include "rti_kernels.hpp"
@@ -205,44 +206,18 @@ hipError_t launch_plant(const ModelConst& P, const double* mcf, int B, int wind_
 // per launch at the driver's shape) and loads a command's three controls when it
 // arrives; the row is compacted at exit, when the RK4 registers are dead.  What
 // the flight loop carries beyond k_plant's registers is two counters.
-static_assert(KITE_DELAY_DEPTH == 4 && KITE_DELAY_NLINE == 32 && KITE_DELAY_U == KITE_DELAY_T_ARR + KITE_DELAY_DEPTH &&
-              KITE_DELAY_U + NU * KITE_DELAY_DEPTH <= KITE_DELAY_NLINE && NU == 4, "the line's layout");
+static_assert(NU == kLineNU, "the line's layout (delay_line.hpp)");
 
-// the send: t_arr = max(t_send, t_arr_prev) + tau (the sequential sleep of
-// TDelay::publish: the channel never reorders); returns the pending count
-__device__ __forceinline__ int delay_send(double* L, const double* __restrict__ u_cmd, const double* __restrict__ tau,
-                                          int i, double t0, int32_t& flag) {
-    const double c = L[KITE_DELAY_COUNT];
-    int n = c >= 1.0 ? (c >= (double)KITE_DELAY_DEPTH ? KITE_DELAY_DEPTH : (int)c) : 0;   // NaN: 0
-    if (u_cmd) {
-        const double ta = tau[i];
-        if (!(ta >= 0.0) || !isfinite(ta)) {
-            flag |= KITE_PLANT_BAD_TAU;         // the command is dropped
-        } else {
-            const double prev = L[KITE_DELAY_HAS_PREV] != 0.0 ? L[KITE_DELAY_T_PREV] : t0;
-            const double t_arr = fmax(t0, prev) + ta;
-            if (n == KITE_DELAY_DEPTH) {        // full: the oldest goes (circular_buffer::push_back)
-                for (int s = 0; s + 1 < KITE_DELAY_DEPTH; ++s) {
-                    L[KITE_DELAY_T_ARR + s] = L[KITE_DELAY_T_ARR + s + 1];
-                    for (int q = 0; q < NU; ++q) L[KITE_DELAY_U + NU * s + q] = L[KITE_DELAY_U + NU * (s + 1) + q];
-                }
-                n = KITE_DELAY_DEPTH - 1;
-                flag |= KITE_PLANT_CMD_DROPPED;
-            }
-            L[KITE_DELAY_T_ARR + n] = t_arr;
-            for (int q = 0; q < NU; ++q) L[KITE_DELAY_U + NU * n + q] = u_cmd[(size_t)i * NU + q];
-            ++n;
-            L[KITE_DELAY_T_PREV] = t_arr;
-            L[KITE_DELAY_HAS_PREV] = 1.0;
-        }
-    }
-    return n;
-}
+// the send (delay_line.hpp: delay_send) appends the command under the line's
+// arrival rule, slot KITE_DELAY_RULE: sequential, t_arr = max(t_send,
+// t_arr_prev) + tau, or transport, t_arr = max(t_send + tau, t_arr_prev).  The
+// rule is the line's, so one launch may mix both
 
 // the line at the call's end.  What has left the FIFO by the last tick does
 // not depend on the flight (a frozen kite's line goes on): the pops the flight
 // did not get to are made up here.  Then the last arrival becomes the control
-// in force, the rest moves to the front and vacated slots are zeroed.  The
+// in force, the rest moves to the front and vacated slots are zeroed (the
+// rule slot is not touched: the line keeps its rule).  The
 // whole row comes into registers with one round of loads (the RK4 registers
 // are dead by now) and the new row is selected with compares, not indexed: a
 // chain of dependent loads and stores per slot costs more than the flight's

@@ -19,6 +19,7 @@
 
 #include <type_traits>
 
+#include "delay_line.hpp"
 #include "kite_model.hpp"
 #include "kite_model_dp.hpp"
 #include "rti_kernels.hpp"
@@ -99,7 +100,8 @@ __device__ __forceinline__ void prologue_kite(const ModelConst& P, const RtiCons
                                               const double* __restrict__ x0in, double* __restrict__ X,
                                               double* __restrict__ U, int32_t* __restrict__ status,
                                               const double* __restrict__ wind, int32_t* __restrict__ cold,
-                                              double* sx0, double* sUv, int* sWarm_, int B = 0) {
+                                              double* sx0, double* sUv, int* sWarm_, int B = 0,
+                                              const double* __restrict__ sched = nullptr) {
     int& sWarm = *sWarm_;
     const int l = threadIdx.x;
     const int N = C.N;
@@ -139,10 +141,43 @@ __device__ __forceinline__ void prologue_kite(const ModelConst& P, const RtiCons
             // transport-delay compensation (nmpf_node.cpp:206-221): predict the
             // measured kite state over `delay` under the previous u(t0); theta,
             // thetadot from the previous trajectory at t0 + delay
-            const double up[NU] = {Ub[0], Ub[1], Ub[2], 0.0};
+            //
+            // With an in-flight schedule (sched, k_inflight's rows; kite_nmpc.h)
+            // the control is piecewise constant over the window: the control in
+            // force, then the line's pending commands from their arrival
+            // offsets on.  One loop over the pieces serves both: without a
+            // schedule (or with an invalid row) it is one piece of length
+            // delay under the previous u(t0), delay_steps substeps of
+            // delay / delay_steps
+            double up[NU] = {Ub[0], Ub[1], Ub[2], 0.0};
+            const double* row = nullptr;
+            int nsw = 0;
+            if (sched) {
+                row = sched + (size_t)b * KITE_INFLIGHT_N;
+                const double c = row[0];
+                if (c >= 0.0) {
+                    nsw = c < (double)KITE_DELAY_DEPTH ? (int)c : KITE_DELAY_DEPTH;
+                    for (int j = 0; j < 3; ++j) up[j] = row[5 + j];
+                } else {
+                    st |= KITE_ST_BAD_INFLIGHT;
+                }
+            }
+            const double h_max = C.delay / C.delay_steps;
             double xp[NX];
-            if (wind) rk4_primal<true>(P, x0, up, C.delay / C.delay_steps, C.delay_steps, xp, wind + 3 * b);
-            else rk4_primal(P, x0, up, C.delay / C.delay_steps, C.delay_steps, xp);
+            for (int i = 0; i < NX; ++i) xp[i] = x0[i];
+            double a = 0.0;
+            for (int seg = 0; seg <= nsw; ++seg) {
+                const double e = seg < nsw ? fmin(row[1 + seg], C.delay) : C.delay;    // a switch at or after the end is none
+                const double len = e - a;
+                if (len > 0.0) {            // a command superseded at the same instant never flies
+                    const int ns = inflight_substeps(len, h_max, C.delay_steps);
+                    if (wind) rk4_primal<true>(P, xp, up, len / ns, ns, xp, wind + 3 * b);
+                    else rk4_primal(P, xp, up, len / ns, ns, xp);
+                    a = e;
+                }
+                if (seg < nsw)
+                    for (int j = 0; j < 3; ++j) up[j] = row[8 + 3 * seg + j];
+            }
             for (int i = 0; i < 13; ++i) x0[i] = xp[i];
             x0[13] = Xb[C.delay_node * NX + 13];
             x0[14] = Xb[C.delay_node * NX + 14];
@@ -220,12 +255,13 @@ __device__ __forceinline__ void prologue_kite(const ModelConst& P, const RtiCons
 __global__ __launch_bounds__(64) void k_prologue(ModelConst P, RtiConst C, int B, int warm,
                                                  const double* __restrict__ x0in,
                                                  double* __restrict__ X, double* __restrict__ U,
-                                                 int32_t* __restrict__ status, const double* __restrict__ wind) {
+                                                 int32_t* __restrict__ status, const double* __restrict__ wind,
+                                                 const double* __restrict__ sched) {
     __shared__ double sx0[NX];
     __shared__ double sUv[KITE_NMAX];
     __shared__ int sWarm;
     if ((int)blockIdx.x >= B) return;
-    prologue_kite<true>(P, C, blockIdx.x, warm, x0in, X, U, status, wind, nullptr, sx0, sUv, &sWarm);
+    prologue_kite<true>(P, C, blockIdx.x, warm, x0in, X, U, status, wind, nullptr, sx0, sUv, &sWarm, 0, sched);
 }
 // warm step, no delay compensation (run_step's common case)
 __global__ __launch_bounds__(64) void k_prologue_warm(ModelConst P, RtiConst C, int B,
@@ -244,13 +280,14 @@ __global__ __launch_bounds__(64) void k_prologue_cold(ModelConst P, RtiConst C, 
                                                       double* __restrict__ X, double* __restrict__ U,
                                                       int32_t* __restrict__ status,
                                                       const double* __restrict__ wind,
-                                                      const int32_t* __restrict__ cold, int B) {
+                                                      const int32_t* __restrict__ cold, int B,
+                                                      const double* __restrict__ sched) {
     __shared__ double sx0[NX];
     __shared__ double sUv[KITE_NMAX];
     __shared__ int sWarm;
     const int n = min(cold[0], B);
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        prologue_kite<true>(P, C, cold[1 + i], 1, x0in, X, U, status, wind, nullptr, sx0, sUv, &sWarm);
+        prologue_kite<true>(P, C, cold[1 + i], 1, x0in, X, U, status, wind, nullptr, sx0, sUv, &sWarm, 0, sched);
         __syncthreads();
     }
 }
@@ -270,20 +307,22 @@ static_assert(kModelConstDoubles < MCT_STRIDE, "a table row holds a ModelConst a
 __global__ __launch_bounds__(64) void k_prologue_pk(const double* __restrict__ mct, RtiConst C, int B, int warm,
                                                     const double* __restrict__ x0in,
                                                     double* __restrict__ X, double* __restrict__ U,
-                                                    int32_t* __restrict__ status, const double* __restrict__ wind) {
+                                                    int32_t* __restrict__ status, const double* __restrict__ wind,
+                                                    const double* __restrict__ sched) {
     __shared__ double sx0[NX];
     __shared__ double sUv[KITE_NMAX];
     __shared__ int sWarm;
     if ((int)blockIdx.x >= B) return;
     const ModelConst P = model_row(mct, blockIdx.x);
-    prologue_kite<true>(P, C, blockIdx.x, warm, x0in, X, U, status, wind, nullptr, sx0, sUv, &sWarm);
+    prologue_kite<true>(P, C, blockIdx.x, warm, x0in, X, U, status, wind, nullptr, sx0, sUv, &sWarm, 0, sched);
 }
 __global__ __launch_bounds__(64) void k_prologue_cold_pk(const double* __restrict__ mct, RtiConst C,
                                                          const double* __restrict__ x0in,
                                                          double* __restrict__ X, double* __restrict__ U,
                                                          int32_t* __restrict__ status,
                                                          const double* __restrict__ wind,
-                                                         const int32_t* __restrict__ cold, int B) {
+                                                         const int32_t* __restrict__ cold, int B,
+                                                         const double* __restrict__ sched) {
     __shared__ double sx0[NX];
     __shared__ double sUv[KITE_NMAX];
     __shared__ int sWarm;
@@ -292,7 +331,7 @@ __global__ __launch_bounds__(64) void k_prologue_cold_pk(const double* __restric
         const int b = __builtin_amdgcn_readfirstlane(cold[1 + i]);
         if (b < 0 || b >= B) continue;      // block-uniform
         const ModelConst P = model_row(mct, b);
-        prologue_kite<true>(P, C, b, 1, x0in, X, U, status, wind, nullptr, sx0, sUv, &sWarm);
+        prologue_kite<true>(P, C, b, 1, x0in, X, U, status, wind, nullptr, sx0, sUv, &sWarm, 0, sched);
         __syncthreads();
     }
 }
@@ -2160,22 +2199,37 @@ __global__ __launch_bounds__(64, 2) void k_closest_point(RtiConst C, int count, 
 // ---------------------------------------------------------------------------
 hipError_t launch_prologue(const ModelConst& P, const RtiConst& C, int B, int warm, const double* x0,
                            double* X, double* U, int32_t* status, const double* wind, int32_t* cold,
-                           const double* mct, hipStream_t s) {
+                           const double* mct, const double* sched, hipStream_t s) {
     constexpr int PRO_COLD_GRID = 256;
     if (warm && !(C.delay > 0.0)) {
         // (k_prologue_warm compiles no simulation: it needs no model)
         hipLaunchKernelGGL(k_prologue_warm, dim3(B), dim3(64), 0, s, P, C, B, x0, X, U, status, cold);
         if (mct)
             hipLaunchKernelGGL(k_prologue_cold_pk, dim3(B < PRO_COLD_GRID ? B : PRO_COLD_GRID), dim3(64), 0, s, mct,
-                               C, x0, X, U, status, wind, cold, B);
+                               C, x0, X, U, status, wind, cold, B, sched);
         else
             hipLaunchKernelGGL(k_prologue_cold, dim3(B < PRO_COLD_GRID ? B : PRO_COLD_GRID), dim3(64), 0, s, P, C,
-                               x0, X, U, status, wind, cold, B);
+                               x0, X, U, status, wind, cold, B, sched);
     } else if (mct) {
-        hipLaunchKernelGGL(k_prologue_pk, dim3(B), dim3(64), 0, s, mct, C, B, warm, x0, X, U, status, wind);
+        hipLaunchKernelGGL(k_prologue_pk, dim3(B), dim3(64), 0, s, mct, C, B, warm, x0, X, U, status, wind, sched);
     } else {
-        hipLaunchKernelGGL(k_prologue, dim3(B), dim3(64), 0, s, P, C, B, warm, x0, X, U, status, wind);
+        hipLaunchKernelGGL(k_prologue, dim3(B), dim3(64), 0, s, P, C, B, warm, x0, X, U, status, wind, sched);
     }
+    return hipGetLastError();
+}
+
+// the in-flight schedule (kite_nmpc.h, KITE_INFLIGHT_N): one lane per kite
+// turns the kite's command line as it stands at t0 into its row of the
+// context's schedule buffer (delay_line.hpp: inflight_row).  The line is read,
+// not changed
+__global__ __launch_bounds__(64) void k_inflight(int B, const double* __restrict__ line, double t0,
+                                                 double* __restrict__ sched) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= B) return;
+    inflight_row(line + (size_t)i * KITE_DELAY_NLINE, t0, sched + (size_t)i * KITE_INFLIGHT_N);
+}
+hipError_t launch_inflight(int B, const double* line, double t0, double* sched, hipStream_t s) {
+    hipLaunchKernelGGL(k_inflight, dim3((B + 63) / 64), dim3(64), 0, s, B, line, t0, sched);
     return hipGetLastError();
 }
 hipError_t launch_rk4_sens(const ModelConst& P, const RtiConst& C, int B, const double* X, const double* U,

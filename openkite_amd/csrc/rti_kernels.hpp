@@ -79,9 +79,14 @@ hipError_t launch_qp_ric(const RtiConst& C, const RicConst& R, const RtiConst* C
 // mct: per-kite model constants, kite-major [B][kModelTableStride] doubles (a
 // kite's ModelConst and a pad), or nullptr: every kite takes P (kernel
 // argument).  With a table the sensitivities are fp64 only (C.sens_fp32 == 0).
+// sched: the in-flight schedule, B x KITE_INFLIGHT_N (launch_inflight), or
+// nullptr: the delay compensation predicts under the previous u(t0)
 hipError_t launch_prologue(const ModelConst& P, const RtiConst& C, int B, int warm, const double* x0,
                            double* X, double* U, int32_t* status, const double* wind, int32_t* cold,
-                           const double* mct, hipStream_t s);
+                           const double* mct, const double* sched, hipStream_t s);
+// sched (B x KITE_INFLIGHT_N) <- the schedule rows of the lines (B x
+// KITE_DELAY_NLINE) seen at time t0 (k_inflight; delay_line.hpp)
+hipError_t launch_inflight(int B, const double* line, double t0, double* sched, hipStream_t s);
 hipError_t launch_rk4_sens(const ModelConst& P, const RtiConst& C, int B, const double* X, const double* U,
                            double* AB, double* DEF, const double* wind, const double* mct, hipStream_t s);
 constexpr int kModelTableStride = 48;

@@ -34,7 +34,10 @@ One step of a fleet of kites on one rank:
          a per-kite command line (transport_delay.cpp) and the kite flies what
          has arrived (kite_nmpc_plant_step_delayed_device, still one launch);
          the estimators propagate under that control, ``restart`` resets the
-         lines, and a ``recorder`` logs it (accepted only where it is constant
+         lines (fresh lines are empty schedules), and with ``delay_comp="queue"``
+         the RTI's delay compensation predicts under the commands still in the
+         line (kite_nmpc_set_inflight_device right before the step) instead of
+         the last u(t0) alone; a ``recorder`` logs what flew (accepted only where it is constant
          over a period: no jitter, a mean of whole periods).
 
   adapt  with ``recorder`` and ``adapt`` (an ``IdentConfig``): each time the
@@ -110,6 +113,16 @@ class GpuStepper:
         ``wind.stride(0)`` doubles apart, components contiguous)."""
         assert wind.dtype == torch.float64 and wind.stride(1) == 1
         self.ctx.set_wind_device(wind.data_ptr(), wind.stride(0), wmax)
+
+    def set_inflight_device(self, line, t0):
+        """The delay compensation's in-flight schedule from the kites' command
+        lines, a contiguous (B, DELAY_NLINE) device tensor, as they stand at
+        time t0 (kite_nmpc_set_inflight_device); None switches it off."""
+        if line is None:
+            self.ctx.set_inflight_device(0, t0)
+            return
+        assert line.dtype == torch.float64 and line.is_contiguous()
+        self.ctx.set_inflight_device(line.data_ptr(), t0)
 
     def set_params_device(self, rows, status=None):
         """The controller's per-kite models from a contiguous (B, 52) device
@@ -224,13 +237,22 @@ class ActuationDelay:
     ``draw`` takes tau uniform on [max(mean - deviation, 0), mean + deviation]
     (seconds; the reference's transport_delay node, there in ms) from a seeded
     device generator; deviation == 0 draws nothing, tau is the mean.  A command
-    arrives at max(t_send, previous arrival) + tau: a mean above the control
-    period is a channel that falls behind and drops its oldest commands."""
+    arrives at max(t_send, previous arrival) + tau (``rule="sequential"``, the
+    default): a mean above the control period is a channel that falls behind
+    and drops its oldest commands.  ``rule="transport"``: it arrives at
+    max(t_send + tau, previous arrival), a pure transport delay that still
+    never reorders; the rule is written into every line's ``DELAY_RULE`` slot."""
 
-    def __init__(self, B: int, mean: float, deviation: float = 0.0, seed: int = 0, device=None):
+    RULES = {"sequential": 0.0, "transport": 1.0}      # nmpc.DELAY_RULE_*
+
+    def __init__(self, B: int, mean: float, deviation: float = 0.0, seed: int = 0, device=None,
+                 rule: str = "sequential"):
         from . import nmpc
         if not (mean >= 0.0 and math.isfinite(mean)) or not (deviation >= 0.0 and math.isfinite(deviation)):
             raise ValueError("ActuationDelay: mean and deviation are finite and >= 0")
+        if rule not in self.RULES:
+            raise ValueError('ActuationDelay: rule is "sequential" or "transport"')
+        self.rule = rule
         f64 = dict(dtype=torch.float64, device=device)
         self.B, self.mean, self.deviation, self.seed = int(B), float(mean), float(deviation), int(seed)
         self.lo, self.hi = max(self.mean - self.deviation, 0.0), self.mean + self.deviation
@@ -239,10 +261,16 @@ class ActuationDelay:
         self.tau = torch.full((self.B,), self.lo, **f64)
         self.gen = torch.Generator(device=self.line.device)
         self.gen.manual_seed(self.seed)
+        self._rule_slot = nmpc.DELAY_RULE
+        if self.RULES[rule] != 0.0:
+            self.line[:, self._rule_slot] = self.RULES[rule]
 
     def reset(self):
-        """Fresh lines (empty, zero control in force) and the generator back at its seed."""
+        """Fresh lines (empty, zero control in force, the rule in its slot) and
+        the generator back at its seed."""
         self.line.zero_()
+        if self.RULES[self.rule] != 0.0:
+            self.line[:, self._rule_slot] = self.RULES[self.rule]
         self.u_applied.zero_()
         self.gen.manual_seed(self.seed)
 
@@ -385,7 +413,13 @@ class FleetLoop:
                  covariances: Optional[tuple] = None, publisher=None, noise: Optional[MeasurementNoise] = None,
                  plant=None, wind_ekf: bool = False, wind_max: float = 20.0, recorder=None, adapt=None,
                  estimator_model: str = "creation", ident_wind=None, kin_ekf: bool = False,
-                 ident_wind_config=None, scorer=None):
+                 ident_wind_config=None, scorer=None, delay_comp: str = "last"):
+        if delay_comp not in ("last", "queue"):
+            raise ValueError('delay_comp is "last" or "queue"')
+        if delay_comp == "queue" and getattr(plant, "delay", None) is None:
+            raise ValueError('delay_comp="queue" predicts under the commands in the line: it needs a delayed plant '
+                             "(GpuPlant(..., delay=ActuationDelay(...)))")
+        self.delay_comp = delay_comp
         if scorer is not None and scorer.B != x0.shape[0]:
             raise ValueError(f"the scorer holds {scorer.B} kites, the loop flies {x0.shape[0]}")
         if ekf and wind_ekf:
@@ -662,6 +696,10 @@ class FleetLoop:
             self.recorder.record_state(self.x0)
             if self.adapt is not None and self.recorder.full:
                 self._adapt()
+        if self.delay_comp == "queue":
+            # the lines as they stand now, at the instant the state was measured:
+            # this step's delay compensation predicts under what is in flight
+            self.stepper.set_inflight_device(self.delay.line, self.t)
         self.stepper.rti(self.x0, self.u0, self.traj, self.diag, self.status)
         if self.scorer is not None:
             # the true state at t0: the plant's, or without one the state the plan

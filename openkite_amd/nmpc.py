@@ -23,11 +23,16 @@ DEFAULT_PARAMS = os.path.join(REPO, "data", "umx_radian.yaml")
 KITE_OK, KITE_EINVAL, KITE_EHIP, KITE_ENOMEM, KITE_ENODEV, KITE_EIO, KITE_EPARSE, KITE_ESTATE = 0, -1, -2, -3, -4, -5, -6, -7
 ST_NAN, ST_QP_NOT_CONV, ST_MIN_SPEED, ST_STATE_BOUND, ST_THETA_WRAP, ST_STEP_REJECTED = 1, 2, 4, 8, 16, 32
 ST_RESTART = 64
+ST_BAD_INFLIGHT = 128              # KITE_ST_BAD_INFLIGHT: the kite's in-flight schedule row is invalid
+INFLIGHT_N = 24                    # KITE_INFLIGHT_N: doubles per kite of the in-flight schedule
 PLANT_NAN = 1                      # KITE_PLANT_NAN (plant status word)
 PLANT_CMD_DROPPED, PLANT_BAD_TAU = 2, 4    # KITE_PLANT_* of the delayed step: oldest command dropped, bad latency
 # the command line of plant_step_delayed (KITE_DELAY_*): depth, doubles per kite and the slots
 DELAY_DEPTH, DELAY_NLINE = 4, 32
 DELAY_COUNT, DELAY_T_PREV, DELAY_HAS_PREV, DELAY_U_FORCE, DELAY_T_ARR, DELAY_U = 0, 1, 2, 4, 8, 12
+# the line's arrival rule (slot DELAY_RULE): sequential, t_arr = max(t_send, t_arr_prev) + tau, or
+# transport, t_arr = max(t_send + tau, t_arr_prev); exactly 1.0 in the slot is transport, anything else sequential
+DELAY_RULE, DELAY_RULE_SEQUENTIAL, DELAY_RULE_TRANSPORT = 3, 0, 1
 EKF_NAN, EKF_S_NOT_PD = 1, 2       # KITE_EKF_* (status word of the wind-estimating and the kinematic EKF)
 EKF_INIT_BAD = 4                   # KITE_EKF_INIT_BAD (status word of kin_ekf_init)
 WIND_MAX_DEFAULT = 20.0            # set_wind_device: clamp of an estimated wind component, m/s
@@ -336,6 +341,9 @@ _SIGNATURES = {
                                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                            ctypes.c_double, ctypes.c_double, ctypes.c_int32,
                                                            ctypes.c_int32, ctypes.c_void_p]),
+    "kite_nmpc_set_inflight": (ctypes.c_int, [ctypes.c_void_p, _DP, ctypes.c_double]),
+    "kite_nmpc_set_inflight_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]),
+    "kite_nmpc_get_inflight": (ctypes.c_int, [ctypes.c_void_p, _DP]),
     "kite_nmpc_closest_point_global": (ctypes.c_int,[ctypes.c_void_p, ctypes.c_int32, _DP, _DP, _DP]),
     "kite_nmpc_closest_point_global_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                                              ctypes.c_void_p, ctypes.c_void_p]),
@@ -1064,6 +1072,36 @@ class BatchNMPC:
         _check(lib().kite_nmpc_plant_step_delayed_device(self._h, v(x13_ptr), v(u4_cmd_ptr), v(tau_ptr), v(line_ptr),
                                                          v(u4_applied_ptr), float(t0), float(h), int(steps),
                                                          int(substeps), v(status_ptr)), "plant_step_delayed_device")
+
+    # --- the in-flight schedule of the delay compensation ----------------------
+    def set_inflight(self, line, t0: float = 0.0):
+        """The commands in flight as the delay compensation sees them
+        (kite_nmpc_set_inflight): line (B, DELAY_NLINE), the kites' command
+        lines as they stand at time t0, becomes the context's schedule; warm
+        steps with config.delay > 0 then predict under the control in force
+        and the pending commands instead of the previous u(t0).  None switches
+        the schedule off.  It stays in force as stored: refresh it every
+        period, right before the step."""
+        if line is None:
+            _check(lib().kite_nmpc_set_inflight(self._h, None, float(t0)), "set_inflight")
+            return
+        ln = _f64(line)
+        if ln.shape != (self.batch, DELAY_NLINE):
+            raise ValueError(f"line: ({self.batch}, {DELAY_NLINE}) expected, got {ln.shape}")
+        _check(lib().kite_nmpc_set_inflight(self._h, _p(ln), float(t0)), "set_inflight")
+
+    def set_inflight_device(self, line_ptr: int, t0: float = 0.0):
+        """set_inflight from a (B, DELAY_NLINE) device array (asynchronous on the
+        context stream, the line is read in stream order); 0 switches it off."""
+        _check(lib().kite_nmpc_set_inflight_device(self._h, ctypes.c_void_p(line_ptr) if line_ptr else None,
+                                                   float(t0)), "set_inflight_device")
+
+    def get_inflight(self) -> np.ndarray:
+        """The schedule rows in force, (B, INFLIGHT_N): [n | s_1..s_4 | control in
+        force (3) | pending commands (4 x 3) | zeros]; n = -1 marks an invalid row."""
+        out = np.zeros((self.batch, INFLIGHT_N))
+        _check(lib().kite_nmpc_get_inflight(self._h, _p(out)), "get_inflight")
+        return out
 
     # --- aerodynamic parameter identification ---------------------------------
     def _ident_rows(self, params, count: int) -> np.ndarray:
